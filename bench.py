@@ -18,6 +18,12 @@ architectures (no checkpoints offline) and synthetic 30 s / 16 kHz sine clips + 
 
 One process per GPU (torch.distributed.run); each rank processes its own 64 clips (weak scaling),
 gradients are averaged with an RCCL all-reduce; rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, ms_per_step and what the timed
+steps themselves record).  `--full` adds the legs that take runs of their own: the teacher-forward timing and the CPU
+baseline (c2/c3), the eager decode behind the cross-attention roofline (c4/c5).  `--dump-outputs DIR` writes what the
+last timed step returned as DIR/<name>.npy (float32): the losses and a fixed sample of the updated student weights
+(c2/c3), the generated token ids (c4/c5).  Models and inputs are seeded, so the same arguments give the same inputs.
 """
 from __future__ import annotations
 
@@ -98,6 +104,34 @@ def make_batches(args, device, rank, nb=2):
         dec, lab = coll.collate_labels(synthetic_label_lists(args.batch, seed=seed))
         out.append((wav, dec.to(device), lab.to(device)))
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 20           # elements kept of an array too large to write whole
+
+
+def _sample(t, n=DUMP_SAMPLE):
+    """t as it is, or -- above n elements -- the values of the flattened t at n fixed (seed 0, sorted) positions."""
+    import numpy as np
+    t = t.detach()
+    if t.numel() > n:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=n, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write each tensor as <path>/<name>.npy in float32 (token ids and losses are exact or
+    as computed; nothing here exceeds float32)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} limit")
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(seconds_budget=20.0):
@@ -277,18 +311,23 @@ def run_decode(args, device, rank, world, pg):
         B, t_avg = 1, 4 + sum(len(t["raw"]) for t in trace_last) / max(1, 2 * len(trace_last))
     ms_dec = elapsed / dec_steps * 1e3
     step_bytes = decode_bytes_per_step(cfg, B, t_avg)
-    # dominant kernel (cross-attention over the encoder K/V, the largest per-step read): per-launch HIP
-    # events over an eager (non-graph) decode of the same batch shape, 16 steps
-    timer = KernelTimer("decode_attn_cross")
-    with timer:
-        if c4:
-            mel, _ = fe.extract(wavs[0], want_conv_input=False)
-            m.generate(mel, use_graph=False, language="zh", task="transcribe", max_new_tokens=16)
-        else:
-            m.generate(mel_long[:, :, :3000], use_graph=False, return_timestamps=True, language="zh",
-                       task="transcribe", max_new_tokens=16)
-            trace.clear()
-    ks = timer.summary()
+    if args.dump_outputs and rank == 0:
+        # the last timed step's return value: the token ids of every clip / recording (padded rows as returned)
+        dump_outputs(args.dump_outputs, {"tokens": _sample(out, DUMP_LIMIT_BYTES // 4)})
+    ks = None
+    if args.full:
+        # dominant kernel (cross-attention over the encoder K/V, the largest per-step read): per-launch HIP
+        # events over an eager (non-graph) decode of the same batch shape, 16 steps
+        timer = KernelTimer("decode_attn_cross")
+        with timer:
+            if c4:
+                mel, _ = fe.extract(wavs[0], want_conv_input=False)
+                m.generate(mel, use_graph=False, language="zh", task="transcribe", max_new_tokens=16)
+            else:
+                m.generate(mel_long[:, :, :3000], use_graph=False, return_timestamps=True, language="zh",
+                           task="transcribe", max_new_tokens=16)
+                trace.clear()
+        ks = timer.summary()
     if rank == 0:
         value = units_per_step * args.steps * world / elapsed
         roof = None
@@ -429,8 +468,13 @@ def main():
                          "--dtype float16, fp16 autocast + loss scaler)")
     ap.add_argument("--longform-kwargs", default="ref", choices=["ref", "none"],
                     help="c5: run_eval.py:659-665 long-form kwargs (ref) or greedy windows only (none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-teacher-fwd", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: teacher-forward timing and CPU baseline "
+                         "(c2/c3), the eager decode behind the cross-attention roofline (c4/c5)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-teacher-fwd", action="store_true", help="with --full: skip the teacher-forward timing")
     args = ap.parse_args()
     dflt = {"c3": (64, 10, 3), "c2": (32, 10, 3), "c4": (512, 1, 1), "c5": (1, 1, 1)}[args.config]
     args.batch = dflt[0] if args.batch is None else args.batch
@@ -523,8 +567,15 @@ def main():
     ks = timer.summary()
     dist = exchange_summary(trainer.exchange_events, trainer.exchange_log, args.steps, t_rank, pg, world, device)
 
+    if args.dump_outputs and rank == 0:
+        # the last timed step's return value (the three losses) and, since a training step's other product is the
+        # update, a fixed sample of the student's fp32 master weights after it
+        arrays = {k: v.reshape(1) for k, v in m.items()}
+        arrays["student_weights_sample"] = _sample(student.store.p32[:student.train_prefix])
+        dump_outputs(args.dump_outputs, arrays)
+
     teacher_ms = None
-    if not args.no_teacher_fwd:
+    if args.full and not args.no_teacher_fwd:
         # teacher forward (large-v2 encoder + decoder over T_dec 447 + head) ms/clip
         wav, dec, lab = batches[0]
         mel, conv = fe.extract(wav)
@@ -540,7 +591,7 @@ def main():
         teacher_ms = (time.perf_counter() - ta) / 3 / args.batch * 1e3
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:

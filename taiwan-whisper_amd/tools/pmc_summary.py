@@ -54,7 +54,7 @@ def main():
         res[fam] = dict(launches=len(fetch[fam]), fetch_bytes_per_launch=f, write_bytes_per_launch=w,
                         hbm_bytes_per_launch=f + w)
         print(f"{fam:9s} launches={len(fetch[fam]):5d} fetch {f/1e6:9.1f} MB  write {w/1e6:9.1f} MB per launch")
-    res["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over `bench.py --steps 2 --warmup 1`; "
+    res["_note"] = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes over `bench.py --full --steps 2 --warmup 1`; "
                     "FETCH_SIZE x2 (gfx950 wide-read correction), KiB -> bytes.  L2-miss (L2 <-> fabric) bytes: "
                     "Infinity-Cache hits are counted too and no gfx950 counter separates them, so hbm_bytes_per_launch "
                     "is an upper bound of DRAM bytes")

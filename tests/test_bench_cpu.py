@@ -100,6 +100,39 @@ def test_distributed_fields():
     assert d0["rank_exchange_exposed_ms"] == [4.0, 5.0]
 
 
+def test_full_and_dump_outputs_are_options():
+    """`--full` (the legs that take runs of their own) and `--dump-outputs DIR` parse and reach the ranks."""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--dump-outputs", "d"],
+                       env=_env(TW_BENCH_PRINT_LAUNCH=1), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["launch"]
+    assert cmd[cmd.index(BENCH) + 1:] == ["--gpus", "2", "--full", "--dump-outputs", "d"]
+
+
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs writes float32 <name>.npy files; an array above the sample size is cut to the same fixed
+    positions every time, and the 64 MB limit on the whole dump is enforced."""
+    import numpy as np
+    import pytest
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float64)
+    s1, s2 = bench._sample(big), bench._sample(big.clone())
+    assert s1.numel() == bench.DUMP_SAMPLE and torch.equal(s1, s2)
+    assert bool((s1[1:] > s1[:-1]).all())                         # distinct, sorted positions
+    small = torch.tensor([[1, 50257], [3, 4]], dtype=torch.int64)
+    assert torch.equal(bench._sample(small), small)               # below the sample size: whole, shape kept
+    out = tmp_path / "o"
+    bench.dump_outputs(str(out), {"loss": torch.tensor([1.5], dtype=torch.float64), "tokens": bench._sample(small)})
+    assert sorted(p.name for p in out.iterdir()) == ["loss.npy", "tokens.npy"]
+    tok = np.load(out / "tokens.npy")
+    assert tok.dtype == np.float32 and tok.tolist() == [[1.0, 50257.0], [3.0, 4.0]]
+    assert np.load(out / "loss.npy").tolist() == [1.5]
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(out), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+
+
 def test_single_rank_summary():
     sys.path.insert(0, REPO)
     import bench
