@@ -93,6 +93,29 @@ int tw_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const vo
                 int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK,
                 int64_t lddk, void* dV, int64_t lddv, int B, int H, int Tq, int Tk, int head_dim, int causal,
                 float scale, float* workspace /* B*H*Tq floats */, tw_stream_t stream);
+/* The same kernels over PACKED rows (the trainer's decoder: clip b keeps only its first n_b rows, the clips
+ * concatenated).  offq: B + 1 cumulative query-row offsets (device int32): clip b's Q / O / dO / dQ rows are
+ * offq[b] .. offq[b+1]-1; Mq = offq[B]; max_q = the longest clip (the grid's extent).  offk: the same for the
+ * K / V / dK / dV rows (causal self-attention passes the query array), or NULL for dense keys at b*Tk (cross-attention);
+ * Tk = the dense key count, or with offk the longest clip.  lse and the backward's workspace are [H][Mq] fp32 (entry
+ * h*Mq + offq[b] + q).  Each clip's rows equal the dense entry called on that clip alone (B = 1) bit for bit; a clip
+ * without queries gets zero dK / dV rows; nothing past row Mq is written.  _f16: fp16 tensors. */
+int tw_attn_fwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
+                       int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H, int Mq, int max_q, int Tk,
+                       int head_dim, int causal, float scale, tw_stream_t stream);
+int tw_attn_fwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
+                           int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
+                           int Tk, int head_dim, int causal, float scale, tw_stream_t stream);
+int tw_attn_bwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                       const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                       int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq, const int* offk,
+                       int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                       float* workspace /* H*Mq floats */, tw_stream_t stream);
+int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                           const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                           int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
+                           const int* offk, int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
+                           float scale, float* workspace, tw_stream_t stream);
 
 /* Fused CE + temperature KL loss and its logits gradient (replaces run_distillation.py:1507-1516,
  * :1539-1549 and HF CE :1082-1087).  out3 = [loss, ce, kl*T^2]; dlogits (same dtype as the logits:
@@ -121,6 +144,17 @@ int tw_embed_fwd(const int64_t* ids, const void* tok, int tok_dtype, const void*
                  int out_dtype, int rows, int T, int pos_offset, int D, tw_stream_t stream);
 int tw_embed_bwd(const int64_t* ids, const float* dh, float* dE, int rows, int D, int64_t padding_idx,
                  tw_stream_t stream);
+/* Packed decoder rows.  tw_pack_plan: from labels [B][T], n_b = 1 + the last t with labels[b][t] >= 0 (0 without
+ * one); off[0..B] (int32) = the running sum of n_b; src_rows[off[b] + t] = b*T + t for t < n_b, the padded row each
+ * packed row came from (B*T entries, those past off[B] set to 0).
+ * tw_embed_fwd_rows: tw_embed_fwd where row r takes position src_rows[r] % T.
+ * tw_pos_grad_rows: gP[t] += sum over clips b with t < n_b of dx[off[b] + t] (fp32, clips in ascending order);
+ * max_rows = the longest clip. */
+int tw_pack_plan(const int64_t* labels, int B, int T, int* off, int64_t* src_rows, tw_stream_t stream);
+int tw_embed_fwd_rows(const int64_t* ids, const int64_t* src_rows, const void* tok, int tok_dtype, const void* pos,
+                      int pos_dtype, void* out, int out_dtype, int rows, int T, int pos_offset, int D,
+                      tw_stream_t stream);
+int tw_pos_grad_rows(const float* dx, const int* off, int B, int max_rows, int D, float* gP, tw_stream_t stream);
 
 /* dst[c][r] = src[r][c], bf16 [rows][cols] (row stride ld_src) -> [cols][rows] (ld_dst): the tied
  * embedding as the K-major operand of the LM-head input gradient (dh = dlogits . E, K = vocabulary). */

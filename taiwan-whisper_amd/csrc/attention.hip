@@ -6,7 +6,7 @@
 //
 // Layout: rows of [B*T][ld] with head h at columns h*64 .. h*64+63, so Q/K/V are read
 // in place from the fused QKV (or KV) projection output and O is written where out_proj
-// reads it.  LSE [B][H][Tq] (natural log of the scaled-score row sum) is kept for the
+// reads it.  LSE [B][H][Tq] ([H][rows] for packed rows: AttnP) (natural log of the scaled-score row sum) is kept for the
 // backward pass.
 //
 // MFMA v_mfma_f32_16x16x32_bf16 in the "swapped" orientation: S^T = K·Q^T, so each lane
@@ -86,7 +86,25 @@ struct AttnP {
   int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
   int B, H, Tq, Tk, causal;
   float scale, scale_log2;
+  // Packed rows (the VL instantiations, tw_attn_*_varlen): B + 1 cumulative row offsets.  With offq, clip b's
+  // queries (Q, O, dO, dQ) are rows offq[b] .. offq[b+1]-1 of their matrices and Tq is only the longest clip (the
+  // grid's extent); with offk the keys (K, V, dK, dV) likewise, else they stay dense at b*Tk.  Both null: dense.
+  // lse and Dv are then [H][Mq] (Mq = offq[B], every packed query row): entry h*Mq + offq[b] + q.
+  const int* offq; const int* offk;
+  int Mq;
 };
+
+// rows of clip b: dense [b*T, b*T + T), or [off[b], off[b+1]) of a packed matrix
+template <bool VL>
+__device__ __forceinline__ void clip_rows(const int* off, int b, int& T, int64_t& row0) {
+  row0 = (int64_t)b * T;
+  if constexpr (VL) {
+    if (off) {
+      row0 = off[b];
+      T = off[b + 1] - off[b];
+    }
+  }
+}
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -111,7 +129,9 @@ __device__ __forceinline__ float fmx(float a, float b) { return __builtin_elemen
 // K/V arrive in a 3-deep LDS ring: two tiles in flight (prefetch distance 2: the DMA of tile kt+2 overlaps the
 // compute of tiles kt and kt+1), counted vmcnt + a raw s_barrier (a __syncthreads() would drain every DMA in
 // flight).  (Round 3's opt-in lazy max and the 2-stage ring were deleted in round 4: DESIGN.md, Attention.)
-template <bool H>
+// VL: packed rows (AttnP::offq / offk); the grid spans the longest clip and a block past its clip's last query
+// leaves at once (workgroup-uniform, before any LDS-DMA or barrier)
+template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   constexpr int ST = 3;
   __shared__ __attribute__((aligned(16))) char smem[ST * 2 * TB];   // [ST stages][K, V]
@@ -122,16 +142,22 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   const int b = bh / p.H, h = bh % p.H;
   const int qblk = xblk * QB;
   const int qw = qblk + wave * QW;
-  const bf16* Qb = p.Q + (int64_t)b * p.Tq * p.ldq + h * 64;
-  const bf16* Kb = p.K + (int64_t)b * p.Tk * p.ldk + h * 64;
-  const bf16* Vb = p.V + (int64_t)b * p.Tk * p.ldv + h * 64;
-  const int off = p.Tk - p.Tq;   // causal diagonal offset
+  int Tq = p.Tq, Tk = p.Tk;
+  int64_t qrow0, krow0;
+  clip_rows<VL>(p.offq, b, Tq, qrow0);
+  clip_rows<VL>(p.offk, b, Tk, krow0);
+  if (VL && qblk >= Tq) return;
+  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
+  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
+  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
+  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
+  const int off = Tk - Tq;   // causal diagonal offset
 
   bf16x8 qf[2][2];
 #pragma unroll
   for (int qi = 0; qi < 2; ++qi)
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) qf[qi][kk] = ld_frag(Qb, p.ldq, qw + qi * 16 + li, p.Tq, kk, lane);
+    for (int kk = 0; kk < 2; ++kk) qf[qi][kk] = ld_frag(Qb, p.ldq, qw + qi * 16 + li, Tq, kk, lane);
 
   f32x4 o[4][2];
 #pragma unroll
@@ -140,9 +166,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
     for (int j = 0; j < 2; ++j) o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[2] = {NEG_BIG, NEG_BIG}, l[2] = {0.f, 0.f};
 
-  int nkt = (p.Tk + KT - 1) / KT;
+  int nkt = (Tk + KT - 1) / KT;
   if (p.causal) {
-    const int qmax = min(p.Tq - 1, qblk + QB - 1);
+    const int qmax = min(Tq - 1, qblk + QB - 1);
     const int kend = qmax + off + 1;
     nkt = min(nkt, (kend + KT - 1) / KT);
   }
@@ -150,8 +176,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   auto stage = [&](int buf, int kt) {
     char* Ks = smem + buf * 2 * TB;
     const int k0 = kt * KT;
-    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, p.Tk - k0, Ks, wave, lane);
-    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, p.Tk - k0, Ks + TB, wave, lane);
+    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, Tk - k0, Ks, wave, lane);
+    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, Tk - k0, Ks + TB, wave, lane);
   };
   // S^T = K Q^T for one tile, boundary tiles masked (key tail / causal diagonal)
   auto scores = [&](const bf16x8 (&kf)[4][2], f32x4 (&s)[4][2], int k0) {
@@ -161,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
       s[kj][0] = mma16<H>(kf[kj][1], qf[0][1], mma16<H>(kf[kj][0], qf[0][0], z));
       s[kj][1] = mma16<H>(kf[kj][1], qf[1][1], mma16<H>(kf[kj][0], qf[1][0], z));
     }
-    const bool need_mask = (k0 + KT > p.Tk) || (p.causal && k0 + KT - 1 > qw + off);
+    const bool need_mask = (k0 + KT > Tk) || (p.causal && k0 + KT - 1 > qw + off);
     if (need_mask) {
 #pragma unroll
       for (int qi = 0; qi < 2; ++qi) {
@@ -171,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = k0 + kj * 16 + 4 * g + r;
-            const bool ok = key < p.Tk && (!p.causal || key <= q + off);
+            const bool ok = key < Tk && (!p.causal || key <= q + off);
             if (!ok) s[kj][qi][r] = -INFINITY;
           }
       }
@@ -277,15 +303,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   for (int qi = 0; qi < 2; ++qi) {
     const float lt = swap32_sum(swap16_sum(l[qi]));   // xor 16 then 32 on permlane swaps (bit-identical: common.h)
     const int q = qw + qi * 16 + li;
-    if (q < p.Tq) {
+    if (q < Tq) {
       const float inv = 1.f / lt;
-      bf16* Ob = p.O + ((int64_t)b * p.Tq + q) * p.ldo + h * 64;
+      bf16* Ob = p.O + (qrow0 + q) * p.ldo + h * 64;
 #pragma unroll
       for (int hj = 0; hj < 4; ++hj) {
         const f32x4 v = o[hj][qi] * inv;
         *(bf16x4*)(Ob + hj * 16 + 4 * g) = bf16x4{f2e<H>(v[0]), f2e<H>(v[1]), f2e<H>(v[2]), f2e<H>(v[3])};
       }
-      if (g == 0 && p.lse) p.lse[(int64_t)bh * p.Tq + q] = (m[qi] + log2f(lt)) / LOG2E;
+      if (g == 0 && p.lse) p.lse[lse0 + q] = (m[qi] + log2f(lt)) / LOG2E;
     }
   }
 }
@@ -295,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
 // dQ: per query block, loop over key tiles (K, V in LDS).  Also computes D[q] = sum_e dO[q][e] O[q][e] for its rows
 // (each lane's 16 products, then the 4 lanes of a row by xor-16 / xor-32 swaps) and stores it for the dK/dV kernel,
 // which runs after it: no separate pass over dO and O.
-template <bool H>
+template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
   const int lane = lane_id(), wave = wave_id_uniform();
@@ -305,13 +331,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   const int b = bh / p.H, h = bh % p.H;
   const int qblk = xblk * QB;
   const int qw = qblk + wave * QW;
-  const bf16* Qb = p.Q + (int64_t)b * p.Tq * p.ldq + h * 64;
-  const bf16* dOb = p.dO + (int64_t)b * p.Tq * p.lddo + h * 64;
-  const bf16* Kb = p.K + (int64_t)b * p.Tk * p.ldk + h * 64;
-  const bf16* Vb = p.V + (int64_t)b * p.Tk * p.ldv + h * 64;
-  const int off = p.Tk - p.Tq;
+  int Tq = p.Tq, Tk = p.Tk;
+  int64_t qrow0, krow0;
+  clip_rows<VL>(p.offq, b, Tq, qrow0);
+  clip_rows<VL>(p.offk, b, Tk, krow0);
+  if (VL && qblk >= Tq) return;
+  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
+  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
+  const bf16* dOb = p.dO + qrow0 * p.lddo + h * 64;
+  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
+  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
+  const int off = Tk - Tq;
 
-  const bf16* Ob = p.O + (int64_t)b * p.Tq * p.ldo + h * 64;
+  const bf16* Ob = p.O + qrow0 * p.ldo + h * 64;
   bf16x8 qf[2][2], dof[2][2];
   float lse2[2], Dq[2];
 #pragma unroll
@@ -320,15 +352,15 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     float dd = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      qf[qi][kk] = ld_frag(Qb, p.ldq, q, p.Tq, kk, lane);
-      dof[qi][kk] = ld_frag(dOb, p.lddo, q, p.Tq, kk, lane);
-      const bf16x8 of = ld_frag(Ob, p.ldo, q, p.Tq, kk, lane);
+      qf[qi][kk] = ld_frag(Qb, p.ldq, q, Tq, kk, lane);
+      dof[qi][kk] = ld_frag(dOb, p.lddo, q, Tq, kk, lane);
+      const bf16x8 of = ld_frag(Ob, p.ldo, q, Tq, kk, lane);
 #pragma unroll
       for (int e = 0; e < 8; ++e) dd += e2f<H>(dof[qi][kk][e]) * e2f<H>(of[e]);
     }
-    lse2[qi] = q < p.Tq ? p.lse[(int64_t)bh * p.Tq + q] * LOG2E : 0.f;
+    lse2[qi] = q < Tq ? p.lse[lse0 + q] * LOG2E : 0.f;
     Dq[qi] = swap32_sum(swap16_sum(dd));                 // rows past Tq: zero fragments, D = 0
-    if (g == 0 && q < p.Tq) p.Dv[(int64_t)bh * p.Tq + q] = Dq[qi];
+    if (g == 0 && q < Tq) p.Dv[lse0 + q] = Dq[qi];
   }
   f32x4 dq[4][2];
 #pragma unroll
@@ -336,16 +368,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) dq[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  int nkt = (p.Tk + KT - 1) / KT;
+  int nkt = (Tk + KT - 1) / KT;
   if (p.causal) {
-    const int qmax = min(p.Tq - 1, qblk + QB - 1);
+    const int qmax = min(Tq - 1, qblk + QB - 1);
     nkt = min(nkt, (qmax + off + 1 + KT - 1) / KT);
   }
   auto stage = [&](int buf, int kt) {
     char* Ks = smem + buf * 2 * TB;
     const int k0 = kt * KT;
-    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, p.Tk - k0, Ks, wave, lane);
-    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, p.Tk - k0, Ks + TB, wave, lane);
+    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, Tk - k0, Ks, wave, lane);
+    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, Tk - k0, Ks + TB, wave, lane);
   };
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -372,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     const int k0 = kt * KT;
     // P recomputed with the forward's exp2 (v_exp_f32) and, on interior tiles (no key tail, no query tail, not on
     // the causal diagonal: wave-uniform), without the per-element mask
-    const bool need_mask = (k0 + KT > p.Tk) || (qw + QW > p.Tq) || (p.causal && k0 + KT - 1 > qw + off);
+    const bool need_mask = (k0 + KT > Tk) || (qw + QW > Tq) || (p.causal && k0 + KT - 1 > qw + off);
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
       const int q = qw + qi * 16 + li;
@@ -381,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = k0 + kj * 16 + 4 * g + r;
-          const bool ok = !need_mask || (key < p.Tk && q < p.Tq && (!p.causal || key <= q + off));
+          const bool ok = !need_mask || (key < Tk && q < Tq && (!p.causal || key <= q + off));
           // masked scores as exp2(-inf) = 0: a select, not a branch per element (interior tiles: ok is always true)
           const float pr = __builtin_amdgcn_exp2f(ok ? s[kj][qi][r] * p.scale_log2 - lse2[qi] : -INFINITY);
           s[kj][qi][r] = pr * (dp[kj][qi][r] - Dq[qi]);   // dS^T
@@ -405,8 +437,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 #pragma unroll
   for (int qi = 0; qi < 2; ++qi) {
     const int q = qw + qi * 16 + li;
-    if (q < p.Tq) {
-      bf16* out = p.dQ + ((int64_t)b * p.Tq + q) * p.lddq + h * 64;
+    if (q < Tq) {
+      bf16* out = p.dQ + (qrow0 + q) * p.lddq + h * 64;
 #pragma unroll
       for (int hj = 0; hj < 4; ++hj) {
         const f32x4 v = dq[hj][qi] * p.scale;
@@ -420,7 +452,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 // Two workgroups per CU (round 4): 218 VGPRs, two waves per SIMD hide each other's LDS / exp / MFMA latencies.  At
 // one workgroup per CU (round 3: 268-276 VGPRs, accumulators shuffled through AGPRs) the encoder-shape backward
 // took 6.1 ms against 4.6 ms now (tools/bench_attn.py, same box, profiles/r04_h_attn_bwd_ab.log).
-template <bool H>
+template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TB + 2 * 2 * 64 * 4];
   const int lane = lane_id(), wave = wave_id_uniform();
@@ -430,11 +462,17 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   const int b = bh / p.H, h = bh % p.H;
   const int kblk = xblk * QB;
   const int kw = kblk + wave * QW;
-  const bf16* Qb = p.Q + (int64_t)b * p.Tq * p.ldq + h * 64;
-  const bf16* dOb = p.dO + (int64_t)b * p.Tq * p.lddo + h * 64;
-  const bf16* Kb = p.K + (int64_t)b * p.Tk * p.ldk + h * 64;
-  const bf16* Vb = p.V + (int64_t)b * p.Tk * p.ldv + h * 64;
-  const int off = p.Tk - p.Tq;
+  int Tq = p.Tq, Tk = p.Tk;
+  int64_t qrow0, krow0;
+  clip_rows<VL>(p.offq, b, Tq, qrow0);
+  clip_rows<VL>(p.offk, b, Tk, krow0);
+  if (VL && kblk >= Tk) return;     // a clip without queries still writes its (zero) dK / dV rows below
+  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
+  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
+  const bf16* dOb = p.dO + qrow0 * p.lddo + h * 64;
+  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
+  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
+  const int off = Tk - Tq;
   float* rowc = (float*)(smem + 4 * TB);   // [2 stages][lse2 64 | D 64]
 
   bf16x8 kf[2][2], vf[2][2];
@@ -442,8 +480,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   for (int kj = 0; kj < 2; ++kj)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      kf[kj][kk] = ld_frag(Kb, p.ldk, kw + kj * 16 + li, p.Tk, kk, lane);
-      vf[kj][kk] = ld_frag(Vb, p.ldv, kw + kj * 16 + li, p.Tk, kk, lane);
+      kf[kj][kk] = ld_frag(Kb, p.ldk, kw + kj * 16 + li, Tk, kk, lane);
+      vf[kj][kk] = ld_frag(Vb, p.ldv, kw + kj * 16 + li, Tk, kk, lane);
     }
   f32x4 dk[4][2], dv[4][2];
 #pragma unroll
@@ -451,7 +489,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
 #pragma unroll
     for (int j = 0; j < 2; ++j) dk[i][j] = dv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int nqt_all = (p.Tq + KT - 1) / KT;
+  const int nqt_all = (Tq + KT - 1) / KT;
   int qt0 = 0;
   if (p.causal) {
     const int qmin = kblk - off;   // first query that can see this key block
@@ -460,12 +498,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   auto stage = [&](int buf, int qt) {
     char* Qs = smem + buf * 2 * TB;
     const int q0 = qt * KT;
-    stage_tile(Qb + (int64_t)q0 * p.ldq, p.ldq, p.Tq - q0, Qs, wave, lane);
-    stage_tile(dOb + (int64_t)q0 * p.lddo, p.lddo, p.Tq - q0, Qs + TB, wave, lane);
+    stage_tile(Qb + (int64_t)q0 * p.ldq, p.ldq, Tq - q0, Qs, wave, lane);
+    stage_tile(dOb + (int64_t)q0 * p.lddo, p.lddo, Tq - q0, Qs + TB, wave, lane);
     if (threadIdx.x < 64) {
       const int q = q0 + threadIdx.x;
-      rowc[buf * 128 + threadIdx.x] = q < p.Tq ? p.lse[(int64_t)bh * p.Tq + q] * LOG2E : 0.f;
-      rowc[buf * 128 + 64 + threadIdx.x] = q < p.Tq ? p.Dv[(int64_t)bh * p.Tq + q] : 0.f;
+      rowc[buf * 128 + threadIdx.x] = q < Tq ? p.lse[lse0 + q] * LOG2E : 0.f;
+      rowc[buf * 128 + 64 + threadIdx.x] = q < Tq ? p.Dv[lse0 + q] : 0.f;
     }
   };
   if (qt0 < nqt_all) {
@@ -496,7 +534,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
       }
     }
     // interior tiles (no query tail, no key tail, not on the causal diagonal: wave-uniform) skip the mask
-    const bool need_mask = (q0 + KT > p.Tq) || (kw + QW > p.Tk) || (p.causal && kw + QW - 1 > q0 + off);
+    const bool need_mask = (q0 + KT > Tq) || (kw + QW > Tk) || (p.causal && kw + QW - 1 > q0 + off);
 #pragma unroll
     for (int qf = 0; qf < 4; ++qf)
 #pragma unroll
@@ -507,7 +545,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
 #pragma unroll
         for (int kj = 0; kj < 2; ++kj) {
           const int key = kw + kj * 16 + li;
-          const bool ok = !need_mask || (q < p.Tq && key < p.Tk && (!p.causal || key <= q + off));
+          const bool ok = !need_mask || (q < Tq && key < Tk && (!p.causal || key <= q + off));
           const float pr = __builtin_amdgcn_exp2f(ok ? s[qf][kj][r] * p.scale_log2 - l2 : -INFINITY);   // select, no branch
           s[qf][kj][r] = pr;                              // P
           dp[qf][kj][r] = pr * (dp[qf][kj][r] - Dq);      // dS
@@ -536,9 +574,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
 #pragma unroll
   for (int kj = 0; kj < 2; ++kj) {
     const int key = kw + kj * 16 + li;
-    if (key < p.Tk) {
-      bf16* ok_ = p.dK + ((int64_t)b * p.Tk + key) * p.lddk + h * 64;
-      bf16* ov_ = p.dV + ((int64_t)b * p.Tk + key) * p.lddv + h * 64;
+    if (key < Tk) {
+      bf16* ok_ = p.dK + (krow0 + key) * p.lddk + h * 64;
+      bf16* ov_ = p.dV + (krow0 + key) * p.lddv + h * 64;
 #pragma unroll
       for (int hj = 0; hj < 4; ++hj) {
         const f32x4 a = dk[hj][kj] * p.scale;
@@ -570,7 +608,7 @@ extern "C" int tw_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ld
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
   p.scale = scale; p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL(attn_fwd_kernel<false>, dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<false, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -588,7 +626,7 @@ extern "C" int tw_attn_fwd_f16(const void* Q, int64_t ldq, const void* K, int64_
   p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
   p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
   p.scale = scale; p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+  hipLaunchKernelGGL((attn_fwd_kernel<true, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -612,11 +650,11 @@ int attn_bwd_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const v
   p.scale = scale; p.scale_log2 = scale * LOG2E;
   // dQ (and D, which the dK/dV kernel reads) first, then dK/dV
   if (half) {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<true>, dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, false>), dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL(attn_bwd_dkdv_kernel<false>, dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false>), dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
   }
   TW_CHECK_LAUNCH();
   return TW_OK;
@@ -639,4 +677,103 @@ extern "C" int tw_attn_bwd_f16(const void* Q, int64_t ldq, const void* K, int64_
                                int Tk, int head_dim, int causal, float scale, float* workspace, hipStream_t stream) {
   return attn_bwd_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, B, H, Tq, Tk,
                       head_dim, causal, scale, workspace, true, stream);
+}
+
+// ------------------------------------------------------------------------------------
+// Packed rows (the trainer's decoder: clip b holds only its first n_b rows, the clips concatenated).  offq: B + 1
+// cumulative query-row offsets (device, int32), Mq = offq[B], max_q = the longest clip.  offk: the same for the
+// keys (causal self-attention passes one array for both), or null for dense keys at b*Tk (cross-attention against
+// the encoder's 1500 rows); Tk is the dense key count, or with offk the longest clip's.  lse (and the backward's
+// workspace) are [H][Mq].  The per-clip tile order is the dense kernels', so every clip's rows equal a dense call
+// on that clip alone bit for bit.  A clip without queries gets zero dK / dV rows.
+namespace {
+bool varlen_args_ok(const int* offq, int B, int Mq, int max_q, int Tk, int causal) {
+  return offq != nullptr && B > 0 && Mq >= 0 && max_q >= 0 && max_q <= Mq && Tk >= 0 && !(causal && max_q > Tk);
+}
+
+int attn_fwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
+                        int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
+                        int Tk, int head_dim, int causal, float scale, bool half, hipStream_t stream) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
+  if (Mq == 0 || max_q == 0 || Tk == 0) return TW_OK;
+  if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
+  AttnP p = {};
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O; p.lse = lse;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+  p.B = B; p.H = H; p.Tq = max_q; p.Tk = Tk; p.causal = causal;
+  p.scale = scale; p.scale_log2 = scale * LOG2E;
+  p.offq = offq; p.offk = offk; p.Mq = Mq;
+  const dim3 grid((max_q + QB - 1) / QB, B * H);
+  if (half) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, stream, p);
+  else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, stream, p);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+// workspace: H*Mq floats
+int attn_bwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                        const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                        int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq, const int* offk,
+                        int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                        float* workspace, bool half, hipStream_t stream) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
+  if (Tk == 0) return TW_OK;
+  if (!check_common(Q, K, V, ldq, ldk, ldv) || ((uintptr_t)dO & 15) || (lddo & 7) || ((uintptr_t)O & 15) || (ldo & 7))
+    return TW_EINVAL;
+  AttnP p = {};
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.lse = (float*)lse; p.O = (bf16*)O;
+  p.dO = (const bf16*)dO; p.Dv = workspace; p.dQ = (bf16*)dQ; p.dK = (bf16*)dK; p.dV = (bf16*)dV;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+  p.B = B; p.H = H; p.Tq = max_q; p.Tk = Tk; p.causal = causal;
+  p.scale = scale; p.scale_log2 = scale * LOG2E;
+  p.offq = offq; p.offk = offk; p.Mq = Mq;
+  const dim3 gq((max_q + QB - 1) / QB, B * H), gk((Tk + QB - 1) / QB, B * H);
+  // dQ (and D) first, then dK/dV; with dense keys the dK/dV launch runs even when no clip has a query (zeros)
+  if (half) {
+    if (max_q > 0) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), gk, dim3(256), 0, stream, p);
+  } else {
+    if (max_q > 0) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), gk, dim3(256), 0, stream, p);
+  }
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+}  // namespace
+
+extern "C" int tw_attn_fwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                  void* O, int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H,
+                                  int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                                  hipStream_t stream) {
+  return attn_fwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, head_dim, causal,
+                             scale, false, stream);
+}
+
+extern "C" int tw_attn_fwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                      int64_t ldv, void* O, int64_t ldo, float* lse, const int* offq, const int* offk,
+                                      int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                                      hipStream_t stream) {
+  return attn_fwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, head_dim, causal,
+                             scale, true, stream);
+}
+
+extern "C" int tw_attn_bwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                  const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                                  int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
+                                  const int* offk, int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
+                                  float scale, float* workspace, hipStream_t stream) {
+  return attn_bwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, offq, offk, B,
+                             H, Mq, max_q, Tk, head_dim, causal, scale, workspace, false, stream);
+}
+
+extern "C" int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                      int64_t ldv, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                      const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV,
+                                      int64_t lddv, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
+                                      int Tk, int head_dim, int causal, float scale, float* workspace,
+                                      hipStream_t stream) {
+  return attn_bwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, offq, offk, B,
+                             H, Mq, max_q, Tk, head_dim, causal, scale, workspace, true, stream);
 }

@@ -46,11 +46,12 @@ __device__ __forceinline__ Stats shfl_stats(const Stats& s, int o) {
   return r;
 }
 
+// S and dS carry no __restrict__: the trainer passes one buffer for both (the gradient overwrites the student logits)
 template <typename E>
-__global__ __launch_bounds__(NT) void klce_kernel(const E* __restrict__ S, const E* __restrict__ Tl, int64_t ld,
+__global__ __launch_bounds__(NT) void klce_kernel(const E* S, const E* __restrict__ Tl, int64_t ld,
                                                   const int64_t* __restrict__ labels, int V, float T, float ce_w,
                                                   float kl_w, const int* __restrict__ n_valid, float grad_scale,
-                                                  float* __restrict__ row_out, E* __restrict__ dS) {
+                                                  float* __restrict__ row_out, E* dS) {
   __shared__ Stats red[NT / 64];
   const int64_t row = blockIdx.x;
   const int64_t lab = labels[row];

@@ -23,6 +23,68 @@ __global__ void embed_fwd_kernel(const int64_t* __restrict__ ids, const void* __
   }
 }
 
+// Packed decoder rows (the trainer drops every clip's trailing label padding: DESIGN.md §4).  From labels [B][T]:
+// n_b = 1 + the last t with labels[b][t] >= 0 (0 without one), off[0..B] = their running sum, and for packed row
+// r = off[b] + t the padded row it came from, src[r] = b*T + t (entries off[B] .. B*T-1 are set to 0, a valid row).
+// One workgroup: a wave per clip for n_b, one thread for the B-term running sum, a wave per clip for src.
+__global__ __launch_bounds__(1024) void pack_plan_kernel(const int64_t* __restrict__ labels, int B, int T, int* off,
+                                                         int64_t* __restrict__ src) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  for (int b = wv; b < B; b += 16) {
+    int n = 0;
+    for (int t = lane; t < T; t += 64)
+      if (labels[(int64_t)b * T + t] >= 0) n = t + 1;      // t ascends: the lane's last hit
+    for (int o = 32; o > 0; o >>= 1) n = max(n, __shfl_xor(n, o, 64));
+    if (lane == 0) off[b + 1] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+    off[0] = 0;
+    for (int b = 0; b < B; ++b) {
+      s += off[b + 1];
+      off[b + 1] = s;
+    }
+  }
+  __syncthreads();
+  for (int b = wv; b < B; b += 16) {
+    const int r0 = off[b], n = off[b + 1] - r0;
+    for (int t = lane; t < n; t += 64) src[r0 + t] = (int64_t)b * T + t;
+  }
+  for (int64_t i = off[B] + threadIdx.x; i < (int64_t)B * T; i += 1024) src[i] = 0;
+}
+
+// embed_fwd_kernel for packed rows: row r sits at position src[r] % T of its clip
+__global__ void embed_fwd_rows_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ src,
+                                      const void* __restrict__ tok, int tok_dtype, const void* __restrict__ pos,
+                                      int pos_dtype, void* __restrict__ out, int out_dtype, int rows, int T,
+                                      int pos_offset, int D) {
+  const int row = blockIdx.x;
+  if (row >= rows) return;
+  const int64_t id = ids[row];
+  const int t = (int)(src[row] % T) + pos_offset;
+  for (int e = threadIdx.x; e < D; e += blockDim.x) {
+    const float a = ld_as_f32(tok, tok_dtype, id * D + e);
+    const float b = ld_as_f32(pos, pos_dtype, (int64_t)t * D + e);
+    st_from_f32(out, out_dtype, (int64_t)row * D + e, a + b);
+  }
+}
+
+// position-embedding gradient of packed rows: gP[t] += sum over clips b with t < n_b of dx[off[b] + t], fp32, clips in
+// ascending order (deterministic)
+__global__ __launch_bounds__(256) void pos_grad_rows_kernel(const float* __restrict__ dx, const int* __restrict__ off,
+                                                            int B, int D, float* __restrict__ gP) {
+  const int t = blockIdx.x;
+  const int e = blockIdx.y * 256 + threadIdx.x;
+  if (e >= D) return;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) {
+    const int r0 = off[b];
+    if (t < off[b + 1] - r0) acc += dx[(int64_t)(r0 + t) * D + e];
+  }
+  gP[(int64_t)t * D + e] += acc;
+}
+
 // H: fp16 words (fp16 autocast's weight cast), else bf16
 template <bool H>
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ src, bf16* __restrict__ dst, int64_t n) {
@@ -252,6 +314,32 @@ extern "C" int tw_embed_fwd(const int64_t* ids, const void* tok, int tok_dtype, 
   if (rows <= 0) return TW_OK;
   hipLaunchKernelGGL(embed_fwd_kernel, dim3(rows), dim3(256), 0, stream, ids, tok, tok_dtype, pos, pos_dtype, out,
                      out_dtype, rows, T, pos_offset, D);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+extern "C" int tw_pack_plan(const int64_t* labels, int B, int T, int* off, int64_t* src_rows, hipStream_t stream) {
+  if (B <= 0 || T <= 0) return TW_EINVAL;
+  hipLaunchKernelGGL(pack_plan_kernel, dim3(1), dim3(1024), 0, stream, labels, B, T, off, src_rows);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+extern "C" int tw_embed_fwd_rows(const int64_t* ids, const int64_t* src_rows, const void* tok, int tok_dtype,
+                                 const void* pos, int pos_dtype, void* out, int out_dtype, int rows, int T,
+                                 int pos_offset, int D, hipStream_t stream) {
+  if (rows <= 0) return TW_OK;
+  if (T <= 0) return TW_EINVAL;
+  hipLaunchKernelGGL(embed_fwd_rows_kernel, dim3(rows), dim3(256), 0, stream, ids, src_rows, tok, tok_dtype, pos,
+                     pos_dtype, out, out_dtype, rows, T, pos_offset, D);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+extern "C" int tw_pos_grad_rows(const float* dx, const int* off, int B, int max_rows, int D, float* gP,
+                                hipStream_t stream) {
+  if (B <= 0 || max_rows <= 0 || D <= 0) return TW_OK;
+  hipLaunchKernelGGL(pos_grad_rows_kernel, dim3(max_rows, (D + 255) / 256), dim3(256), 0, stream, dx, off, B, D, gP);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }

@@ -29,6 +29,16 @@ SIGNATURES = {
     "tw_attn_fwd": [P, I64, P, I64, P, I64, P, I64, P, I32, I32, I32, I32, I32, I32, F32, P],
     "tw_attn_bwd": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, I32, I32, I32, I32,
                     I32, I32, F32, P, P],
+    # packed decoder rows (the trainer drops trailing label padding)
+    "tw_attn_fwd_varlen": [P, I64, P, I64, P, I64, P, I64, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P],
+    "tw_attn_fwd_varlen_f16": [P, I64, P, I64, P, I64, P, I64, P, P, P, I32, I32, I32, I32, I32, I32, I32, F32, P],
+    "tw_attn_bwd_varlen": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, P, P, I32, I32, I32,
+                           I32, I32, I32, I32, F32, P, P],
+    "tw_attn_bwd_varlen_f16": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, P, P, I32, I32,
+                               I32, I32, I32, I32, I32, F32, P, P],
+    "tw_pack_plan": [P, I32, I32, P, P, P],
+    "tw_embed_fwd_rows": [P, P, P, I32, P, I32, P, I32, I32, I32, I32, I32, P],
+    "tw_pos_grad_rows": [P, P, I32, I32, I32, P, P],
     "tw_kl_ce": [P, P, I64, I32, P, I64, I32, F32, F32, F32, P, F32, P, P, P, P],
     "tw_logmel": [P, I32, P, P, P, P, P, P, P],
     "tw_logmel_len": [P, I32, I64, P, P, P, P, P, P, P],

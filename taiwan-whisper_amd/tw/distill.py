@@ -11,6 +11,7 @@ Everything runs on the GPU through libtw_hip.so; nothing on the step synchronise
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Optional
@@ -18,7 +19,7 @@ from typing import Optional
 import torch
 
 from . import ops as F
-from .modeling import Backward, WhisperForConditionalGeneration, is_pseudo
+from .modeling import Backward, PackedRows, WhisperForConditionalGeneration, is_pseudo
 
 
 def constant_with_warmup(step: int, warmup: int) -> float:
@@ -156,6 +157,12 @@ class DistillationTrainer:
             if overlap_update:
                 raise ValueError("overlap_update: the fp16 loss scaler decides each update on the host")
             self.overlap_update = False
+        # Packed decoder rows: the collator pads every label row to max_target_length; the rows after a
+        # clip's last label reach no loss term and, the decoder being causal, no earlier row, so the decoder passes,
+        # the LM heads, the loss and the backward run on the M = sum(n_b) rows before them.  16-bit compute modes;
+        # TW_PACK_ROWS=0 keeps the padded rows (A/B runs).
+        self.pack_rows = student.compute != "fp32" and os.environ.get("TW_PACK_ROWS", "1") != "0"
+        self._pin = {}           # B -> pinned int32 [B+1]: the host copy of the step's row offsets
         self.skipped_steps = 0   # fp16: optimizer steps skipped for a non-finite gradient (GradScaler)
         self._update = None      # (lr, t) of a launched, not yet applied update
         # bench.py instrumentation: with lists here, wait_grad_exchange() appends (start, layers done, tail done)
@@ -201,16 +208,48 @@ class DistillationTrainer:
             return ci                       # the feed's log-mel kernel emitted it in the compute dtype
         return self.s.conv_input(batch["input_features"])
 
-    def _teacher_logits(self, conv_in, ids, labels, enc16, Tk):
+    def _teacher_logits(self, conv_in, ids, labels, enc16, Tk, pk=None):
+        """ids, labels: the padded [B, T] tensors; with pk the teacher decodes their packed rows."""
         t = self.t
         if self.share:
             t_ids = torch.empty_like(labels)
             F.shift_tokens_right(labels, t_ids, t.config.pad_token_id, t.config.decoder_start_token_id)
-            ht = t.decode(t_ids, enc16, Tk)
+            ht = t.decode(t_ids if pk is None else pk.pack(t_ids), enc16, Tk, pk=pk)
         else:
             enc_t = t.encode(conv_in)
-            ht = t.decode(ids, enc_t, Tk)
+            ht = t.decode(ids if pk is None else pk.pack(ids), enc_t, Tk, pk=pk)
         return t.lm_head(ht)
+
+    def _plan_rows(self, batch_labels, labels):
+        """Start the packed-rows plan of this step's labels (device [B, T]) -> a callable that returns the PackedRows
+        descriptor, or None when no row carries a label.  The clip lengths are needed on the host (grids, buffer
+        sizes): labels that arrived on the CPU give them at once; for device labels the offsets computed by
+        tw_pack_plan are copied to pinned memory asynchronously and the callable waits for that copy -- call it after
+        the encoder forward has been queued, so the GPU has that work while the host waits."""
+        B, T = labels.shape
+        off = torch.empty(B + 1, dtype=torch.int32, device=labels.device)
+        src = torch.empty(B * T, dtype=torch.int64, device=labels.device)
+        F.pack_plan(labels, off, src)
+        def descriptor(lens):
+            pk = PackedRows(lens, off, src, T)
+            return pk if pk.M > 0 else None
+
+        if not batch_labels.is_cuda:
+            pos = torch.arange(1, T + 1, dtype=torch.int64)
+            lens = ((batch_labels >= 0) * pos).amax(1).tolist()
+            return lambda: descriptor(lens)
+        host = self._pin.get(B)
+        if host is None:
+            host = self._pin[B] = torch.empty(B + 1, dtype=torch.int32).pin_memory()
+        host.copy_(off, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+
+        def done():
+            ev.synchronize()
+            o = host.tolist()
+            return descriptor([o[b + 1] - o[b] for b in range(B)])
+        return done
 
     def train_step(self, batch, temperature: Optional[float] = None, end_of_dataloader: bool = False):
         """One micro-step: student fwd + teacher fwd + fused KL/CE + backward (+ DP exchange,
@@ -225,9 +264,11 @@ class DistillationTrainer:
         ids = batch["decoder_input_ids"].to(s.device).contiguous()
         labels = batch["labels"].to(s.device).contiguous()
         B, Td = ids.shape
+        plan = self._plan_rows(batch["labels"], labels) if self.pack_rows else None
         enc_tape = [] if self.train_encoder else None
         enc16 = s.encode(conv_in, tape=enc_tape)
         self.flush()             # the previous update (its exchange ran beside the encoder above)
+        pk = plan() if plan is not None else None    # waits for the clip lengths: the encoder is queued by now
         if self.micro == 0:
             s.grad.zero_()
         # DP: on the micro-step that syncs, each layer's gradient slice is all-reduced as soon as
@@ -237,24 +278,26 @@ class DistillationTrainer:
         self.bw.on_ready = self._grad_ready if (self.dp and sync) else None
         Tk = enc16.shape[0] // B
         tape = []
-        hs = s.decode(ids, enc16, Tk, tape=tape)
-        ls = s.lm_head(hs)
-        with torch.no_grad():
-            lt = self._teacher_logits(conv_in, ids, labels, enc16, Tk)
-        lab = labels.reshape(-1)
-        F.count_valid(lab, self.nvalid)
-        dlogits = ls      # the loss gradient overwrites the student logits in place (tw_kl_ce): one [B*T, V] block less
-        # the loss gradient: 1 / accum (accelerate's backward), the folded DDP mean, and fp16's loss scale
-        # (scaler.scale(loss).backward(): the scale enters the fp32 gradient before its fp16 rounding)
-        gs = (self.scaler.scale if self.scaler is not None else 1.0) / (self.accum * (self.world if self.fold_world
-                                                                                         else 1))
-        out3, _ = F.kl_ce(ls, lt, lab, s.config.vocab_size, self.nvalid, T=T, ce_w=0.8, kl_w=self.kl_weight,
-                          grad_scale=gs, dlogits=dlogits)
-        del lt
-        d_enc = torch.zeros(B * Tk, s.config.d_model, dtype=torch.float32, device=s.device) \
-            if self.train_encoder else None
-        self.bw.decoder(tape, dlogits, hs, enc16, d_enc)
-        del tape, dlogits, ls
+        # packed: M changes from step to step; the row buffers keep the padded step's storage size (row_capacity)
+        with self._row_capacity(pk, B * Td):
+            hs = s.decode(ids if pk is None else pk.pack(ids), enc16, Tk, tape=tape, pk=pk)
+            ls = s.lm_head(hs)
+            with torch.no_grad():
+                lt = self._teacher_logits(conv_in, ids, labels, enc16, Tk, pk)
+            lab = labels.reshape(-1) if pk is None else pk.pack(labels)
+            F.count_valid(lab, self.nvalid)
+            dlogits = ls  # the loss gradient overwrites the student logits in place (tw_kl_ce): one [M, V] block less
+            # the loss gradient: 1 / accum (accelerate's backward), the folded DDP mean, and fp16's loss scale
+            # (scaler.scale(loss).backward(): the scale enters the fp32 gradient before its fp16 rounding)
+            gs = (self.scaler.scale if self.scaler is not None else 1.0) / (self.accum * (self.world if self.fold_world
+                                                                                             else 1))
+            out3, _ = F.kl_ce(ls, lt, lab, s.config.vocab_size, self.nvalid, T=T, ce_w=0.8, kl_w=self.kl_weight,
+                              grad_scale=gs, dlogits=dlogits)
+            del lt
+            d_enc = torch.zeros(B * Tk, s.config.d_model, dtype=torch.float32, device=s.device) \
+                if self.train_encoder else None
+            self.bw.decoder(tape, dlogits, hs, enc16, d_enc)
+            del tape, dlogits, ls
         if self.train_encoder:
             self.bw.encoder(enc_tape, d_enc)
         self.micro += 1
@@ -263,6 +306,13 @@ class DistillationTrainer:
             self.micro = 0
         return {"loss": out3[0], "ce_loss": out3[1], "kl_loss": out3[2]}
 
+    def _row_capacity(self, pk, cap):
+        ctx = contextlib.ExitStack()
+        if pk is not None:
+            ctx.enter_context(self.s.row_capacity(cap))
+            ctx.enter_context(self.t.row_capacity(cap))
+        return ctx
+
     def eval_step(self, batch):
         """run_distillation.py:1554-1578: T = 1, no grad."""
         self.flush()
@@ -270,15 +320,18 @@ class DistillationTrainer:
         conv_in = self._conv_input(batch)
         ids = batch["decoder_input_ids"].to(s.device).contiguous()
         labels = batch["labels"].to(s.device).contiguous()
-        B = ids.shape[0]
+        B, Td = ids.shape
+        plan = self._plan_rows(batch["labels"], labels) if self.pack_rows else None
         enc16 = s.encode(conv_in)
+        pk = plan() if plan is not None else None
         Tk = enc16.shape[0] // B
-        ls = s.lm_head(s.decode(ids, enc16, Tk))
-        lt = self._teacher_logits(conv_in, ids, labels, enc16, Tk)
-        lab = labels.reshape(-1)
-        nv = torch.zeros(1, dtype=torch.int32, device=s.device)
-        F.count_valid(lab, nv)
-        out3, _ = F.kl_ce(ls, lt, lab, s.config.vocab_size, nv, T=1.0, ce_w=0.8, kl_w=self.kl_weight)
+        with self._row_capacity(pk, B * Td):
+            ls = s.lm_head(s.decode(ids if pk is None else pk.pack(ids), enc16, Tk, pk=pk))
+            lt = self._teacher_logits(conv_in, ids, labels, enc16, Tk, pk)
+            lab = labels.reshape(-1) if pk is None else pk.pack(labels)
+            nv = torch.zeros(1, dtype=torch.int32, device=s.device)
+            F.count_valid(lab, nv)
+            out3, _ = F.kl_ce(ls, lt, lab, s.config.vocab_size, nv, T=1.0, ce_w=0.8, kl_w=self.kl_weight)
         return {"loss": out3[0], "ce_loss": out3[1], "kl_loss": out3[2]}
 
     # ------------------------------------------------------------------ update

@@ -45,6 +45,36 @@ def padded_vocab(V: int) -> int:
 
 
 
+class PackedRows:
+    """Packed decoder rows: clip b keeps its rows 0 .. lens[b]-1 and the clips are concatenated, M rows
+    in all, in place of the padded [B, T].  lens: host ints; off: device int32 [B+1] running sum of lens; src: device
+    int64, src[r] = b*T + t of packed row r (first M entries); T: the padded length."""
+
+    def __init__(self, lens, off, src, T):
+        self.lens = [int(n) for n in lens]
+        self.B, self.T = len(self.lens), int(T)
+        self.M, self.max_len = sum(self.lens), max(self.lens, default=0)
+        if self.max_len > self.T or min(self.lens, default=0) < 0:
+            raise ValueError("packed rows: a clip length outside [0, T]")
+        if off.dtype != torch.int32 or off.numel() < self.B + 1 or src.dtype != torch.int64 or src.numel() < self.M:
+            raise ValueError("packed rows: off is int32 [B+1], src int64 [>= M]")
+        self.off, self.src = off, src[: self.M]
+
+    @classmethod
+    def from_lens(cls, lens, T, device):
+        """Descriptor from host lengths alone (labels that arrive on the CPU, tests)."""
+        lens = [int(n) for n in lens]
+        off = torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32, device=device)
+        src = torch.tensor([b * T + t for b, n in enumerate(lens) for t in range(n)], dtype=torch.int64, device=device)
+        return cls(lens, off, src, T)
+
+    def pack(self, x):
+        """ids or labels [B, T] -> [M]: one gather by the row index."""
+        if tuple(x.shape) != (self.B, self.T):
+            raise ValueError(f"packed rows: expected [{self.B}, {self.T}], got {tuple(x.shape)}")
+        return x.reshape(-1).index_select(0, self.src)
+
+
 def fp32_compute_supported() -> bool:
     """The fp32-arithmetic path (mixed_precision="no": tw_gemm_f32 / tw_attn_*_f32 and the fp32 variants of
     the loss, decode and selection kernels) is part of libtw_hip.so."""
@@ -439,6 +469,27 @@ class WhisperForConditionalGeneration:
         buf = self.store.p32 if self.compute == "fp32" else self.store.p16
         return self.store.span(buf, first, last, shape)
 
+    _cap = 0     # row capacity of the activation buffers (row_capacity)
+
+    def row_capacity(self, cap: int):
+        """Context: [M, n] activation buffers allocated inside hold max(M, cap) rows of storage.  The packed decoder
+        passes, whose M changes from step to step, then ask the caching allocator for the padded step's block sizes,
+        every step the same: no allocator misses in steady state."""
+        model = self
+
+        class _Ctx:
+            def __enter__(self):
+                self.old, model._cap = model._cap, int(cap)
+
+            def __exit__(self, *exc):
+                model._cap = self.old
+        return _Ctx()
+
+    def _rows(self, M, n, dtype):
+        if self._cap > M:
+            return torch.empty(self._cap, n, dtype=dtype, device=self.device)[:M]
+        return torch.empty(M, n, dtype=dtype, device=self.device)
+
     def _lin(self, x, w, b, out, flags=F.GEMM_ROUND, res=None, aux=None, M=None):
         M = x.shape[0] if M is None else M
         N, K = w.shape
@@ -448,7 +499,7 @@ class WhisperForConditionalGeneration:
         return out
 
     def _ln(self, x, name, out_dtype=None, save=None):
-        y = torch.empty(x.shape, dtype=out_dtype or self.act_dtype, device=self.device)
+        y = self._rows(x.shape[0], x.shape[1], out_dtype or self.act_dtype)
         mean = rstd = None
         if save is not None:
             mean = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
@@ -477,8 +528,8 @@ class WhisperForConditionalGeneration:
         the stream first (in place, or into a fresh buffer when a tape holds the old stream)."""
         if pend is None:
             return x, self._ln(x, name, save=save)
-        xn = x if save is None else torch.empty_like(x)
-        y = torch.empty(x.shape, dtype=self.act_dtype, device=self.device)
+        xn = x if save is None else self._rows(x.shape[0], x.shape[1], x.dtype)
+        y = self._rows(x.shape[0], x.shape[1], self.act_dtype)
         mean = rstd = None
         if save is not None:
             mean = torch.empty(x.shape[0], dtype=torch.float32, device=self.device)
@@ -493,53 +544,62 @@ class WhisperForConditionalGeneration:
         saturation after its MLP residual (HF modeling_whisper.py:409-411), fused into that epilogue."""
         M, N = h.shape[0], w.shape[0]
         if self.defer_residual(kind):
-            r = torch.empty(M, N, dtype=self.act_dtype, device=self.device)
+            r = self._rows(M, N, self.act_dtype)
             self._lin(h, w, b, r)
             return x, r
-        out = torch.empty(M, N, dtype=self.stream_dtype, device=self.device) if tape is not None else x
+        out = self._rows(M, N, self.stream_dtype) if tape is not None else x
         # HF clamps only an fp16 STREAM (modeling_whisper.py:409-411): the fp16 model's, not fp16 autocast's fp32 one
         flags = F.GEMM_ROUND | (F.GEMM_CLAMP16 if clamp and self.stream_dtype == torch.float16 else 0)
         self._lin(h, w, b, out, res=x, flags=flags)
         return out, None
 
-    def _attn_block(self, x, p, B, T, causal, tape=None, pend=None):
-        """x: residual stream [B*T, d] (+ a pending update) -> (new stream, pending update) (self attention)."""
+    def _attn_block(self, x, p, B, T, causal, tape=None, pend=None, pk=None):
+        """x: residual stream [B*T, d] (+ a pending update) -> (new stream, pending update) (self attention).
+        pk: packed rows (PackedRows) -- x holds pk.M rows and the attention runs per clip over its own rows."""
         cfg, d = self.config, self.config.d_model
         H = d // 64
         sv = {} if tape is not None else None
         x, y = self._ln_in(x, pend, p + "_layer_norm", sv)
-        M = B * T
-        qkv = torch.empty(M, 3 * d, dtype=self.act_dtype, device=self.device)
+        M = B * T if pk is None else pk.M
+        qkv = self._rows(M, 3 * d, self.act_dtype)
         wqkv = self.wspan(p + ".q_proj.weight", p + ".v_proj.weight", (3 * d, d))
         bqkv = self.wspan(p + ".q_proj.bias", p + ".v_proj.bias", (3 * d,))
         self._lin(y, wqkv, bqkv, qkv)
-        o = torch.empty(M, d, dtype=self.act_dtype, device=self.device)
-        lse = torch.empty(B * H * T, dtype=torch.float32, device=self.device) if tape is not None else None
-        F.attn_fwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, o, d, lse, B, H, T, T, causal, 0.125)
+        o = self._rows(M, d, self.act_dtype)
+        lse = torch.empty(H * M, dtype=torch.float32, device=self.device) if tape is not None else None
+        if pk is None:
+            F.attn_fwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, o, d, lse, B, H, T, T, causal, 0.125)
+        else:
+            F.attn_fwd_varlen(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, o, d, lse, pk.off, pk.off, pk.B, H,
+                              M, pk.max_len, pk.max_len, causal, 0.125)
         out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
         if tape is not None:
-            tape.append(("attn", p, dict(sv=sv, y=y, qkv=qkv, o=o, lse=lse, B=B, T=T, causal=causal)))
+            tape.append(("attn", p, dict(sv=sv, y=y, qkv=qkv, o=o, lse=lse, B=B, T=T, causal=causal, pk=pk)))
         return out
 
-    def _cross_block(self, x, enc16, p, B, T, Tk, tape=None, kv=None, pend=None):
+    def _cross_block(self, x, enc16, p, B, T, Tk, tape=None, kv=None, pend=None, pk=None):
         d = self.config.d_model
         H = d // 64
         sv = {} if tape is not None else None
         x, y = self._ln_in(x, pend, p + "_layer_norm", sv)
-        M = B * T
-        q = torch.empty(M, d, dtype=self.act_dtype, device=self.device)
+        M = B * T if pk is None else pk.M
+        q = self._rows(M, d, self.act_dtype)
         self._lin(y, self._w16(p + ".q_proj.weight"), self._w16(p + ".q_proj.bias"), q)
         if kv is None:
             kv = torch.empty(B * Tk, 2 * d, dtype=self.act_dtype, device=self.device)
             wkv = self.wspan(p + ".k_proj.weight", p + ".v_proj.weight", (2 * d, d))
             bkv = self.wspan(p + ".k_proj.zero_bias", p + ".v_proj.bias", (2 * d,))
             self._lin(enc16, wkv, bkv, kv)
-        o = torch.empty(M, d, dtype=self.act_dtype, device=self.device)
-        lse = torch.empty(B * H * T, dtype=torch.float32, device=self.device) if tape is not None else None
-        F.attn_fwd(q, d, kv, 2 * d, kv[:, d:], 2 * d, o, d, lse, B, H, T, Tk, False, 0.125)
+        o = self._rows(M, d, self.act_dtype)
+        lse = torch.empty(H * M, dtype=torch.float32, device=self.device) if tape is not None else None
+        if pk is None:
+            F.attn_fwd(q, d, kv, 2 * d, kv[:, d:], 2 * d, o, d, lse, B, H, T, Tk, False, 0.125)
+        else:       # packed queries against the clip's dense Tk encoder rows
+            F.attn_fwd_varlen(q, d, kv, 2 * d, kv[:, d:], 2 * d, o, d, lse, pk.off, None, pk.B, H, M, pk.max_len, Tk,
+                              False, 0.125)
         out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
         if tape is not None:
-            tape.append(("cross", p, dict(sv=sv, y=y, q=q, kv=kv, o=o, lse=lse, B=B, T=T, Tk=Tk)))
+            tape.append(("cross", p, dict(sv=sv, y=y, q=q, kv=kv, o=o, lse=lse, B=B, T=T, Tk=Tk, pk=pk)))
         return out
 
     def _mlp_block(self, x, p, tape=None, pend=None, clamp=False):
@@ -547,8 +607,8 @@ class WhisperForConditionalGeneration:
         sv = {} if tape is not None else None
         x, y = self._ln_in(x, pend, p + ".final_layer_norm", sv)
         f = self.store.segs[p + ".fc1.weight"][0]
-        h = torch.empty(M, f, dtype=self.act_dtype, device=self.device)
-        pre = torch.empty(M, f, dtype=self.act_dtype, device=self.device) if tape is not None else None
+        h = self._rows(M, f, self.act_dtype)
+        pre = self._rows(M, f, self.act_dtype) if tape is not None else None
         self._lin(y, self._w16(p + ".fc1.weight"), self._w16(p + ".fc1.bias"), h, aux=pre,
                   flags=F.GEMM_ROUND | F.GEMM_GELU | (F.GEMM_AUX_OUT if tape is not None else 0))
         out = self._res_out(h, self._w16(p + ".fc2.weight"), self._w16(p + ".fc2.bias"), x, tape, "mlp", clamp=clamp)
@@ -606,8 +666,8 @@ class WhisperForConditionalGeneration:
             tape.append(("ln_final", "model.encoder.layer_norm", dict(sv=sv)))
         return enc
 
-    def embed(self, ids: torch.Tensor) -> torch.Tensor:
-        B, T = ids.shape
+    def embed(self, ids: torch.Tensor, pk=None) -> torch.Tensor:
+        """ids [B, T], or with pk the packed ids [pk.M] (row r at position pk.src[r] % pk.T)."""
         d = self.config.d_model
         if self.store.p32 is not None:
             tok, pos = self.store.v32("model.decoder.embed_tokens.weight"), self.store.v32(
@@ -615,24 +675,37 @@ class WhisperForConditionalGeneration:
         else:
             tok, pos = self.store.v16("model.decoder.embed_tokens.weight"), self.store.v16(
                 "model.decoder.embed_positions.weight")
+        if pk is not None:
+            return F.embed_fwd_rows(ids, pk.src, tok, pos, self._rows(pk.M, d, self.stream_dtype), pk.T)
+        B, T = ids.shape
         x = torch.empty(B * T, d, dtype=self.stream_dtype, device=self.device)
         F.embed_fwd(ids.reshape(-1).contiguous(), tok, pos, x, T)
         return x
 
-    def decode(self, ids: torch.Tensor, enc16: torch.Tensor, Tk: int, tape=None) -> torch.Tensor:
-        """ids [B, T] int64 (device), enc16 [B*Tk, d] -> final decoder hidden [B*T, d] (compute dtype)."""
+    def decode(self, ids: torch.Tensor, enc16: torch.Tensor, Tk: int, tape=None, pk=None) -> torch.Tensor:
+        """ids [B, T] int64 (device), enc16 [B*Tk, d] -> final decoder hidden [B*T, d] (compute dtype).
+        pk (PackedRows, 16-bit compute): ids are the packed [pk.M] ids and the result has pk.M rows; every clip's rows
+        equal those of the padded call (causal self-attention never reads a later row)."""
         cfg = self.config
-        B, T = ids.shape
+        if pk is not None:
+            if self.compute == "fp32":
+                raise ValueError("packed rows: the fp32-compute path keeps padded rows")
+            B, T = pk.B, pk.T
+            if ids.dim() != 1 or ids.numel() != pk.M or enc16.shape[0] != B * Tk:
+                raise ValueError("packed rows: ids must be the packed [M] ids and enc16 hold B*Tk rows")
+        else:
+            B, T = ids.shape
         if T > cfg.max_target_positions:
             raise ValueError("decoder input longer than max_target_positions")
-        x = self.embed(ids)
+        ids = ids.contiguous()
+        x = self.embed(ids, pk)
         if tape is not None:
-            tape.append(("embed", "model.decoder", dict(ids=ids.reshape(-1).contiguous(), B=B, T=T)))
+            tape.append(("embed", "model.decoder", dict(ids=ids.reshape(-1), B=B, T=T, pk=pk)))
         pend = None
         for i in range(cfg.decoder_layers):
             p = f"model.decoder.layers.{i}"
-            x, pend = self._attn_block(x, p + ".self_attn", B, T, True, tape, pend)
-            x, pend = self._cross_block(x, enc16, p + ".encoder_attn", B, T, Tk, tape, pend=pend)
+            x, pend = self._attn_block(x, p + ".self_attn", B, T, True, tape, pend, pk=pk)
+            x, pend = self._cross_block(x, enc16, p + ".encoder_attn", B, T, Tk, tape, pend=pend, pk=pk)
             x, pend = self._mlp_block(x, p, tape, pend)
         sv = {} if tape is not None else None
         _, h = self._ln_in(x, pend, "model.decoder.layer_norm", sv)
@@ -644,7 +717,7 @@ class WhisperForConditionalGeneration:
         """tied proj_out: [M, d] -> logits [M, Vp] in the compute dtype (pad columns are 0)."""
         M = h16.shape[0]
         if out is None:
-            out = torch.empty(M, self.Vp, dtype=self.act_dtype, device=self.device)
+            out = self._rows(M, self.Vp, self.act_dtype)
         E = self._w16("model.decoder.embed_tokens.weight")
         F.gemm(h16, E, out, M, self.Vp, self.config.d_model, lda=h16.stride(0), ldb=self.config.d_model,
                ldc=self.Vp, flags=F.GEMM_ROUND, algo_N=self.config.vocab_size)
@@ -767,7 +840,7 @@ class Backward:
         need = min(1024, (x.shape[0] + 3) // 4) * 2 * D
         if self._ln_ws is None or self._ln_ws.numel() < need:
             self._ln_ws = torch.empty(need, dtype=torch.float32, device=self.dev)
-        g16 = torch.empty(dx.shape, dtype=m.act_dtype, device=self.dev) if m.compute != "fp32" and _LN_G16 else None
+        g16 = m._rows(dx.shape[0], dx.shape[1], m.act_dtype) if m.compute != "fp32" and _LN_G16 else None
         F.layernorm_bwd(x, m.ln_param(name + ".weight"), mean, rstd, dy, dx, m.gv(name + ".weight"),
                         m.gv(name + ".bias"), dx_accum=True, workspace=self._ln_ws, g16=g16)
         self._g16 = (dx, g16) if g16 is not None else None
@@ -794,11 +867,11 @@ class Backward:
         self.dW(g, st["h"], m.gv(p + ".fc2.weight"), M)
         self.db(g, (0, g.shape[1]), m.gv(p + ".fc2.bias"))
         f = st["h"].shape[1]
-        dpre = torch.empty(M, f, dtype=m.act_dtype, device=self.dev)
+        dpre = m._rows(M, f, m.act_dtype)
         self.dX(g, m._w16(p + ".fc2.weight"), dpre, flags=F.GEMM_ROUND | F.GEMM_DGELU, aux=st["pre"])
         self.dW(dpre, st["y"], m.gv(p + ".fc1.weight"), M)
         self.db(dpre, (0, f), m.gv(p + ".fc1.bias"))
-        dy = torch.empty(M, m.config.d_model, dtype=m.act_dtype, device=self.dev)
+        dy = m._rows(M, m.config.d_model, m.act_dtype)
         self.dX(dpre, m._w16(p + ".fc1.weight"), dy)
         self.ln(st["sv"], p + ".final_layer_norm", dy, dx)
 
@@ -806,21 +879,26 @@ class Backward:
         m = self.m
         d = m.config.d_model
         H = d // 64
-        B, T = st["B"], st["T"]
-        M = B * T
+        B, T, pk = st["B"], st["T"], st.get("pk")
+        M = B * T if pk is None else pk.M
         g = self._grad16(dx)
         self.dW(g, st["o"], m.gv(p + ".out_proj.weight"), M)
         self.db(g, (0, d), m.gv(p + ".out_proj.bias"))
-        do = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        do = m._rows(M, d, m.act_dtype)
         self.dX(g, m._w16(p + ".out_proj.weight"), do)
         qkv = st["qkv"]
-        dqkv = torch.empty(M, 3 * d, dtype=m.act_dtype, device=self.dev)
-        F.attn_bwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, st["o"], d, do, d, st["lse"], dqkv, 3 * d,
-                   dqkv[:, d:], 3 * d, dqkv[:, 2 * d:], 3 * d, B, H, T, T, st["causal"], 0.125)
+        dqkv = m._rows(M, 3 * d, m.act_dtype)
+        if pk is None:
+            F.attn_bwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, st["o"], d, do, d, st["lse"], dqkv, 3 * d,
+                       dqkv[:, d:], 3 * d, dqkv[:, 2 * d:], 3 * d, B, H, T, T, st["causal"], 0.125)
+        else:
+            F.attn_bwd_varlen(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, st["o"], d, do, d, st["lse"], dqkv,
+                              3 * d, dqkv[:, d:], 3 * d, dqkv[:, 2 * d:], 3 * d, pk.off, pk.off, pk.B, H, M, pk.max_len,
+                              pk.max_len, st["causal"], 0.125)
         self.dW(dqkv, st["y"], self.span_grad(p + ".q_proj.weight", p + ".v_proj.weight", (3 * d, d)), M)
         self.db(dqkv, (0, d), m.gv(p + ".q_proj.bias"))
         self.db(dqkv, (2 * d, 3 * d), m.gv(p + ".v_proj.bias"))
-        dy = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        dy = m._rows(M, d, m.act_dtype)
         wqkv = m.wspan(p + ".q_proj.weight", p + ".v_proj.weight", (3 * d, d))
         self.dX(dqkv, wqkv, dy)
         self.ln(st["sv"], p + "_layer_norm", dy, dx)
@@ -829,21 +907,25 @@ class Backward:
         m = self.m
         d = m.config.d_model
         H = d // 64
-        B, T, Tk = st["B"], st["T"], st["Tk"]
-        M = B * T
+        B, T, Tk, pk = st["B"], st["T"], st["Tk"], st.get("pk")
+        M = B * T if pk is None else pk.M
         g = self._grad16(dx)
         self.dW(g, st["o"], m.gv(p + ".out_proj.weight"), M)
         self.db(g, (0, d), m.gv(p + ".out_proj.bias"))
-        do = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        do = m._rows(M, d, m.act_dtype)
         self.dX(g, m._w16(p + ".out_proj.weight"), do)
         kv = st["kv"]
-        dq = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        dq = m._rows(M, d, m.act_dtype)
         dkv = torch.empty(B * Tk, 2 * d, dtype=m.act_dtype, device=self.dev)
-        F.attn_bwd(st["q"], d, kv, 2 * d, kv[:, d:], 2 * d, st["o"], d, do, d, st["lse"], dq, d, dkv, 2 * d,
-                   dkv[:, d:], 2 * d, B, H, T, Tk, False, 0.125)
+        if pk is None:
+            F.attn_bwd(st["q"], d, kv, 2 * d, kv[:, d:], 2 * d, st["o"], d, do, d, st["lse"], dq, d, dkv, 2 * d,
+                       dkv[:, d:], 2 * d, B, H, T, Tk, False, 0.125)
+        else:       # every clip's dense dK / dV block is written (zeros for a clip without rows)
+            F.attn_bwd_varlen(st["q"], d, kv, 2 * d, kv[:, d:], 2 * d, st["o"], d, do, d, st["lse"], dq, d, dkv, 2 * d,
+                              dkv[:, d:], 2 * d, pk.off, None, pk.B, H, M, pk.max_len, Tk, False, 0.125)
         self.dW(dq, st["y"], m.gv(p + ".q_proj.weight"), M)
         self.db(dq, (0, d), m.gv(p + ".q_proj.bias"))
-        dy = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        dy = m._rows(M, d, m.act_dtype)
         self.dX(dq, m._w16(p + ".q_proj.weight"), dy)
         self.ln(st["sv"], p + "_layer_norm", dy, dx)
         self.dW(dkv, enc16, self.span_grad(p + ".k_proj.weight", p + ".v_proj.weight", (2 * d, d)), B * Tk)
@@ -854,7 +936,8 @@ class Backward:
 
     # ------------------------------------------------------------------
     def decoder(self, tape, dlogits, h16, enc16, d_enc=None):
-        """dlogits [M, Vp] bf16 -> accumulates every decoder / embedding gradient (and d_enc)."""
+        """dlogits [M, Vp] bf16 -> accumulates every decoder / embedding gradient (and d_enc).  A tape recorded by
+        decode(pk=...) carries its packed-rows descriptor: M = pk.M rows throughout."""
         m = self.m
         d = m.config.d_model
         M = h16.shape[0]
@@ -862,7 +945,7 @@ class Backward:
         gE = m.gv("model.decoder.embed_tokens.weight")
         # LM head (tied): dh = e(dlogits E), dE += e(dlogits^T h) (e = the autocast dtype).  On the 16-bit paths E goes
         # K-major first (one 133 MB transpose): the K = 51 904 product then runs on the persistent kernel
-        dh = torch.empty(M, d, dtype=m.act_dtype, device=self.dev)
+        dh = m._rows(M, d, m.act_dtype)
         if E16.dtype in F.HALF and M >= 4096:
             ET = F.transpose_bf16(E16, torch.empty(d, m.Vp, dtype=E16.dtype, device=self.dev))
             F.gemm(dlogits, ET, dh, M, d, m.Vp, lda=m.Vp, ldb=m.Vp, ldc=d, flags=F.GEMM_ROUND)
@@ -872,7 +955,7 @@ class Backward:
         if gE is not None:
             F.gemm(dlogits, h16, gE, m.Vp, d, M, lda=m.Vp, ldb=d, ldc=d, a_trans=True, b_trans=True,
                    flags=F.GEMM_ROUND | F.GEMM_ACCUM)
-        dx = torch.zeros(M, d, dtype=torch.float32, device=self.dev)
+        dx = m._rows(M, d, torch.float32).zero_()
         for kind, p, st in reversed(tape):
             if kind == "ln_final":
                 self.ln(st["sv"], p, dh, dx)
@@ -888,7 +971,10 @@ class Backward:
                     # HF's decoder embed_tokens has padding_idx = pad_token_id: pad positions add nothing
                     F.embed_bwd(st["ids"], dx, gE, padding_idx=m.config.pad_token_id)
                 gP = m.gv("model.decoder.embed_positions.weight")
-                if gP is not None:   # sum over the batch of position rows
+                pk = st.get("pk")
+                if gP is not None and pk is not None:
+                    F.pos_grad_rows(dx, pk.off, pk.B, pk.M, pk.max_len, gP)
+                elif gP is not None:   # sum over the batch of position rows
                     F.colsum(dx, st["T"] * d, st["B"], st["T"] * d, gP.view(-1), accum=True, round_bf16=False)
         return dx
 

@@ -211,6 +211,54 @@ def attn_bwd(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, 
          int(causal), float(scale), workspace.data_ptr(), _stream())
 
 
+def _varlen_check(offq, offk, B, Mq, max_q, Tk):
+    """-> rows the key-side matrices hold: Mq for packed keys (offk is the query array), else dense B*Tk."""
+    _need(offq, B + 1, "attn offq")
+    assert offq.dtype == torch.int32 and 0 <= max_q <= Mq
+    if offk is None:
+        return B * Tk
+    assert offk.data_ptr() == offq.data_ptr() and Tk == max_q, "packed keys: the self-attention case (offk is offq)"
+    return Mq
+
+
+def attn_fwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, causal, scale):
+    """attn_fwd over packed rows (16-bit only): offq [B+1] int32 device offsets of the clips' query rows, Mq their
+    total and max_q the longest; offk = offq (packed keys, Tk = max_q) or None (dense keys, Tk each).  lse [H][Mq]."""
+    hd = 64
+    Mk = _varlen_check(offq, offk, B, Mq, max_q, Tk)
+    if Mq <= 0:
+        return o
+    for t, ld, rows, nm in ((q, ldq, Mq, "q"), (k, ldk, Mk, "k"), (v, ldv, Mk, "v"), (o, ldo, Mq, "o")):
+        assert t.dtype == q.dtype and t.dtype in HALF, nm
+        _need(t, (rows - 1) * ld + H * hd, f"attn_varlen {nm}")
+    if lse is not None:
+        _need(lse, H * Mq, "attn_varlen lse")
+    call("tw_attn_fwd_varlen_f16" if q.dtype == torch.float16 else "tw_attn_fwd_varlen", q.data_ptr(), ldq,
+         k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse), offq.data_ptr(), _ptr(offk), B, H, Mq,
+         max_q, Tk, hd, int(causal), float(scale), _stream())
+    return o
+
+
+def attn_bwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, dv, lddv, offq, offk, B, H, Mq,
+                    max_q, Tk, causal, scale):
+    """attn_bwd over packed rows (see attn_fwd_varlen); with dense keys every clip's dK / dV block is written."""
+    hd = 64
+    Mk = _varlen_check(offq, offk, B, Mq, max_q, Tk)
+    if Mk <= 0:
+        return
+    for t, ld, rows, nm in ((q, ldq, Mq, "q"), (k, ldk, Mk, "k"), (v, ldv, Mk, "v"), (o, ldo, Mq, "o"),
+                            (do, lddo, Mq, "do"), (dq, lddq, Mq, "dq"), (dk, lddk, Mk, "dk"), (dv, lddv, Mk, "dv")):
+        assert t.dtype == q.dtype and t.dtype in HALF, nm
+        if rows > 0:
+            _need(t, (rows - 1) * ld + H * hd, f"attn_bwd_varlen {nm}")
+    _need(lse, H * Mq, "attn_varlen lse")
+    ws = torch.empty(max(H * Mq, 1), dtype=torch.float32, device=q.device)
+    call("tw_attn_bwd_varlen_f16" if q.dtype == torch.float16 else "tw_attn_bwd_varlen", q.data_ptr(), ldq,
+         k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(), lddo, lse.data_ptr(), dq.data_ptr(),
+         lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, offq.data_ptr(), _ptr(offk), B, H, Mq, max_q, Tk, hd,
+         int(causal), float(scale), ws.data_ptr(), _stream())
+
+
 def kl_ce(s_logits, t_logits, labels, V, n_valid, T=2.0, ce_w=0.8, kl_w=1.0, grad_scale=1.0, dlogits=None,
           row_out=None, out3=None):
     rows, ld = s_logits.shape
@@ -270,6 +318,40 @@ def embed_fwd(ids, tok, pos, out, T, pos_offset=0):
     call("tw_embed_fwd", ids.data_ptr(), tok.data_ptr(), _dt(tok), pos.data_ptr(), _dt(pos), out.data_ptr(),
          _dt(out), rows, T, pos_offset, D, _stream())
     return out
+
+
+def pack_plan(labels, off, src_rows):
+    """labels [B, T] -> off [B+1] int32 (running sum of n_b = 1 + last index with a label >= 0) and src_rows [B*T]
+    int64 (the padded row of each packed row; the first off[B] entries count)."""
+    B, T = labels.shape
+    assert labels.dtype == torch.int64 and labels.is_contiguous() and labels.is_cuda
+    assert off.dtype == torch.int32 and src_rows.dtype == torch.int64
+    _need(off, B + 1, "pack_plan off"); _need(src_rows, B * T, "pack_plan src_rows")
+    call("tw_pack_plan", labels.data_ptr(), B, T, off.data_ptr(), src_rows.data_ptr(), _stream())
+
+
+def embed_fwd_rows(ids, src_rows, tok, pos, out, T, pos_offset=0):
+    """embed_fwd for packed rows: row r sits at position src_rows[r] % T."""
+    rows = ids.numel()
+    D = tok.shape[1]
+    assert ids.dtype == torch.int64 and src_rows.dtype == torch.int64 and ids.is_contiguous()
+    assert out.shape[-1] == D and out.numel() == rows * D and out.is_contiguous()
+    assert pos.shape[0] >= T + pos_offset
+    _need(src_rows, rows, "embed src_rows")
+    call("tw_embed_fwd_rows", ids.data_ptr(), src_rows.data_ptr(), tok.data_ptr(), _dt(tok), pos.data_ptr(), _dt(pos),
+         out.data_ptr(), _dt(out), rows, T, pos_offset, D, _stream())
+    return out
+
+
+def pos_grad_rows(dx, off, B, M, max_rows, gP):
+    """gP[t] += sum over clips b with t < n_b of dx[off[b] + t] (packed rows, fp32, clips in ascending order)."""
+    D = gP.shape[1]
+    assert dx.dtype == torch.float32 and gP.dtype == torch.float32 and off.dtype == torch.int32
+    assert gP.is_contiguous() and gP.shape[0] >= max_rows and 0 <= max_rows <= M
+    _need(off, B + 1, "pos_grad off")
+    if M > 0:
+        _need(dx, M * D, "pos_grad dx")
+    call("tw_pos_grad_rows", dx.data_ptr(), off.data_ptr(), B, max_rows, D, gP.data_ptr(), _stream())
 
 
 def embed_bwd(ids, dh, dE, padding_idx=-1):
