@@ -215,6 +215,21 @@ int tw_decode_attn(const void* q, int64_t sqb, const void* k, int64_t ldk, int64
 int tw_decode_attn_hs(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
                       const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B, int H, int Tk,
                       const int* tk_dev, int head_dim, float scale, int dtype, tw_stream_t stream);
+/* tw_decode_attn_ks: tw_decode_attn_hs with a per-row key start -- k_start is a device array of B int32, and row b
+ * attends keys [k_start[b], Tk) (Tk += *tk_dev as above).  It is the superset form: it takes the head strides, so
+ * one entry serves the row-interleaved self-attention cache (hsk = hsv = 64) and head-major blocks, and with every
+ * start 0 it computes what tw_decode_attn_hs computes (same kernels' bodies, same split rule: fixed Tk and fewer
+ * than 640 (row, head) pairs split the keys into chunks; a chunk wholly below a row's start is empty).  Keys below
+ * the start are never loaded, so a NaN / Inf in a masked K or V row cannot reach the output.  A start >= Tk (or
+ * < 0) is clamped into [0, Tk - 1]: the last key is always attended and nothing outside [0, Tk) is read.  k_start
+ * is read on the device, so a captured step stays valid when its contents change.  This is HF's decoder attention
+ * mask for left-padded prompts (generation_whisper.py _prepare_decoder_input_ids with prompt_ids /
+ * condition_on_prev_tokens): the pad columns' K/V sit in the cache and are masked from then on.  Row b's output is
+ * bit-identical to tw_decode_attn_hs on that row alone with K / V advanced by k_start[b] rows and Tk - k_start[b]
+ * keys (one-workgroup path).  bf16, fp16 and fp32. */
+int tw_decode_attn_ks(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
+                      const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B, int H, int Tk,
+                      const int* tk_dev, const int* k_start, int head_dim, float scale, int dtype, tw_stream_t stream);
 int tw_greedy_select(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
                      const uint32_t* begin_bits, int apply_begin, int64_t eos, uint8_t* done, int64_t* ids,
                      int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col, tw_stream_t stream);
@@ -249,6 +264,12 @@ int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, in
                      tw_stream_t stream);
 int tw_embed_step(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
                   int out_dtype, int B, int D, const int* t_dev, tw_stream_t stream);
+/* tw_embed_step_off: out[b] = tok[ids[b]] + pos[max(*t_dev - pos_off[b], 0)] -- pos_off a device array of B int32,
+ * the left-pad count of each row: positions counted from the row's first real token, the rule HF derives from an
+ * attention mask ((mask.cumsum(-1) - 1).clamp(min=0), generation/utils.py); a padded row then decodes what its
+ * unpadded prompt decodes. */
+int tw_embed_step_off(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
+                      int out_dtype, int B, int D, const int* t_dev, const int* pos_off, tw_stream_t stream);
 /* tw_kv_head_major: the cross-attention K/V as the KV projection writes it (rows b*Tk + t of [B*Tk][ld], k at
  * columns 0..64H, v at 64H..128H) -> dst = K [B][H][Tk][64] followed by V [B][H][Tk][64], so tw_decode_attn reads
  * each (clip, head) as two contiguous runs (called as B*H one-head clips: ldk = 64, skb = Tk*64).  Replaces the

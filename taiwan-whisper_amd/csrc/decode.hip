@@ -75,6 +75,51 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecP p, int nch
   combine_row<E>(p, blockIdx.x, nchunk, ws + (int64_t)blockIdx.x * nchunk * 66);
 }
 
+// per-row key start (left-padded decoder prompts: HF's decoder attention mask): row b attends keys
+// [k_start[b], tk), the start clamped into [0, tk - 1] so at least the last key -- the step's own -- is used and no
+// row below 0 or at / past tk is read.  The body walks from lo, so row b's result is bit-identical to the plain
+// kernel run on that row alone with K / V advanced by k_start[b] rows over tk - k_start[b] keys.
+__device__ __forceinline__ int clamp_start(const int* k_start, int b, int tk) {
+  return max(min(k_start[b], tk - 1), 0);
+}
+template <typename E, int U>
+__device__ __forceinline__ void decode_attn_pair_ks(const DecP& p, const int* k_start) {
+  const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
+  decode_attn_body<E, U, true>(p, b, h, clamp_start(k_start, b, tk), tk, nullptr);
+}
+template <typename E>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_ks_u4_kernel(DecP p, const int* __restrict__ k_start) {
+  decode_attn_pair_ks<E, 4>(p, k_start);
+}
+template <typename E>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_ks_u2_kernel(DecP p, const int* __restrict__ k_start) {
+  decode_attn_pair_ks<E, 2>(p, k_start);
+}
+
+// the split variant: a chunk wholly below the row's start stores the empty partial, as a chunk past tk does; the
+// chunk the start falls into begins there
+template <typename E>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_split_ks_kernel(DecP p, int S, float* ws,
+                                                                          const int* __restrict__ k_start) {
+  const int bh = blockIdx.x, c = blockIdx.y;
+  const int b = bh / p.H, h = bh % p.H;
+  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
+  float* part = ws + ((int64_t)bh * gridDim.y + c) * 66;
+  const int lo = max(c * S, clamp_start(k_start, b, tk)), hi = min(tk, c * S + S);
+  if (lo >= hi) {
+    if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
+    if (threadIdx.x == 0) {
+      part[64] = -INFINITY;
+      part[65] = 0.f;
+    }
+    return;
+  }
+  decode_attn_body<E>(p, b, h, lo, hi, part);
+}
+
 struct SelP {
   const void* logits; int64_t ld;
   int V;
@@ -513,6 +558,21 @@ __global__ void embed_step_kernel(const int64_t* __restrict__ ids, const void* _
   }
 }
 
+// x[b] = tok[ids[b]] + pos[max(*t_dev - pos_off[b], 0)]: a row left-padded by pos_off[b] columns counts its positions
+// from its first real token (the rule HF derives from an attention mask: (mask.cumsum(-1) - 1).clamp(min=0))
+__global__ void embed_step_off_kernel(const int64_t* __restrict__ ids, const void* __restrict__ tok, int tok_dtype,
+                                      const void* __restrict__ pos, int pos_dtype, void* __restrict__ out,
+                                      int out_dtype, int D, const int* __restrict__ t_dev,
+                                      const int* __restrict__ pos_off) {
+  const int b = blockIdx.x;
+  const int64_t id = ids[b];
+  const int64_t t = max(*t_dev - pos_off[b], 0);
+  for (int e = threadIdx.x; e < D; e += blockDim.x) {
+    const float s = ld_as_f32(tok, tok_dtype, id * D + e) + ld_as_f32(pos, pos_dtype, t * D + e);
+    st_from_f32(out, out_dtype, (int64_t)b * D + e, s);
+  }
+}
+
 // cache[b][*t_dev][0:n] = src[b][0:n]   (16-B vectors: 8 bf16 or 4 fp32)
 template <typename E>
 __global__ void kv_append_kernel(const E* __restrict__ src, int64_t ld_src, E* __restrict__ cache,
@@ -642,6 +702,17 @@ extern "C" int tw_embed_step(const int64_t* ids, const void* tok, int tok_dtype,
   return TW_OK;
 }
 
+extern "C" int tw_embed_step_off(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype,
+                                 void* out, int out_dtype, int B, int D, const int* t_dev, const int* pos_off,
+                                 hipStream_t stream) {
+  if (B <= 0) return TW_OK;
+  if (!t_dev || !pos_off || D <= 0) return TW_EINVAL;
+  hipLaunchKernelGGL(embed_step_off_kernel, dim3(B), dim3(256), 0, stream, ids, tok, tok_dtype, pos, pos_dtype, out,
+                     out_dtype, D, t_dev, pos_off);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
 // cross-attention K/V, row-interleaved [rows = B*Tk][ld] (k at columns 0..d, v at d..2d, head h at 64h..) ->
 // head-major dst: K [B][H][Tk][64] then V [B][H][Tk][64] (one (clip, head) reads two contiguous Tk*64 runs)
 template <typename E>
@@ -753,6 +824,45 @@ extern "C" int tw_decode_attn(const void* q, int64_t sqb, const void* k, int64_t
                               int head_dim, float scale, int dtype, hipStream_t stream) {
   return tw_decode_attn_hs(q, sqb, k, ldk, skb, 64, v, ldv, svb, 64, o, sob, B, H, Tk, tk_dev, head_dim, scale, dtype,
                            stream);
+}
+
+// tw_decode_attn_hs with a per-row key start: the same argument checks and the same choice between the split and
+// the one-workgroup-per-pair kernels, so a call with every start 0 computes what tw_decode_attn_hs computes
+extern "C" int tw_decode_attn_ks(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
+                                 const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B,
+                                 int H, int Tk, const int* tk_dev, const int* k_start, int head_dim, float scale,
+                                 int dtype, hipStream_t stream) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (B <= 0 || H <= 0) return TW_OK;
+  if (!k_start) return TW_EINVAL;
+  if ((!tk_dev && Tk <= 0) || Tk > DA_MAX_TK) return TW_EUNSUPPORTED;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
+  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
+  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
+  DecP p;
+  if (dtype == TW_F32 && ((sqb | ldk | skb | ldv | svb) & 3)) return TW_EINVAL;
+  p.q = q; p.sqb = sqb;
+  p.k = k; p.ldk = ldk; p.skb = skb;
+  p.v = v; p.ldv = ldv; p.svb = svb;
+  p.o = o; p.sob = sob;
+  p.hsk = hsk; p.hsv = hsv;
+  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.c = scale * 1.4426950408889634f;
+  const int nchunk = (Tk + DA_SPLIT - 1) / DA_SPLIT;
+  const bool split = !tk_dev && B * H < 640;
+  if (split && nchunk >= 2 && nchunk <= DA_MAX_CHUNK) {
+    float* ws = (float*)tw_device_workspace(stream, (size_t)B * H * nchunk * 66 * sizeof(float));
+    if (ws) {
+      TW_LAUNCH_DT(dtype, decode_attn_split_ks_kernel, dim3(B * H, nchunk), dim3(DA_THREADS), p, DA_SPLIT, ws,
+                   k_start);
+      TW_LAUNCH_DT(dtype, decode_attn_combine_kernel, dim3(B * H), dim3(64), p, nchunk, ws);
+      TW_CHECK_LAUNCH();
+      return TW_OK;
+    }
+  }
+  if (B * H >= DA_BIG) TW_LAUNCH_DT(dtype, decode_attn_ks_u2_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
+  else TW_LAUNCH_DT(dtype, decode_attn_ks_u4_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
 }
 
 extern "C" int tw_greedy_select(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,

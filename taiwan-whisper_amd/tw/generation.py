@@ -75,6 +75,14 @@ class DecodeSession:
         # separate LayerNorm
         self.gemv = B <= 8 and model.compute in ("bf16", "fp16") and d % 256 == 0
         self.gemv_ln = self.gemv and model.stream_dtype == act
+        # left-padded prompts (rows of one batch whose prompts differ in length: HF's decoder attention mask and
+        # position ids): per row the first real cache row and the position offset, read on the device by
+        # tw_decode_attn_ks / tw_embed_step_off.  Allocated once, refilled per window (set_pads), so a captured step
+        # survives; without pad counts the step makes the plain calls
+        self.k_start = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.pos_off = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.padded = False
+        self.shifted = False
 
     def set_encoder(self, enc16):
         """(Re)project the cross-attention K/V of every decoder layer in place (graph-safe).  enc16 holds B*Tk
@@ -110,6 +118,29 @@ class DecodeSession:
             else:
                 m._lin(enc16, wkv, bkv, kv)
         del proj
+
+    def set_pads(self, pads, shift_positions=False):
+        """pads: per-row count of left pad columns of this window's prompt; the pad columns are masked from the
+        row's self-attention.  None: the plain entry points, today's calls.  A list, all zeros included, takes the
+        per-row entries (with every start 0 tw_decode_attn_ks computes the plain entry's result bit for bit), so a
+        caller whose windows alternate between equal and unequal prompt lengths keeps one captured step.
+        shift_positions False (the default): every row embeds at its column index, which is what transformers 5.15
+        computes for Whisper (generate derives position ids from the mask for decoder-only models only,
+        generation/utils.py _prepare_position_ids_for_generation).  True: the row's positions count from its first
+        real token, and the row then decodes exactly what its unpadded prompt decodes.  The captured step bakes in
+        which entry points it calls, so a change of mode drops the graph (recaptured on the next run); the counts
+        themselves are device data."""
+        padded = pads is not None
+        pads = [int(p) for p in pads] if padded else []
+        shifted = padded and bool(shift_positions)
+        if self.graph is not None and (padded != self.padded or shifted != self.shifted):
+            self.graph = None
+        self.padded, self.shifted = padded, shifted
+        if padded:
+            assert len(pads) == self.B and min(pads) >= 0
+            v = torch.tensor(pads, dtype=torch.int32)
+            self.k_start.copy_(v)
+            self.pos_off.copy_(v)
 
     def _ln(self, x, name):
         m = self.m
@@ -147,7 +178,8 @@ class DecodeSession:
         else:
             E, Pe = m.store.v16("model.decoder.embed_tokens.weight"), m.store.v16("model.decoder.embed_positions.weight")
         x, o, t_dev = self.x, self.o, self.t_dev
-        F.embed_step(self.cur, E, Pe, x, t_dev, T_max)
+        ks = self.k_start if self.padded else None
+        F.embed_step(self.cur, E, Pe, x, t_dev, T_max, pos_off=self.pos_off if self.shifted else None)
         sb = T_max * 2 * d
         for i in range(m.config.decoder_layers):
             p = f"model.decoder.layers.{i}"
@@ -162,7 +194,7 @@ class DecodeSession:
                 self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, self.qkv)
                 F.kv_append(self.qkv[:, d:], 3 * d, cache, 2 * d, sb, B, 2 * d, t_dev, T_max)
             F.decode_attn(self.qkv, 3 * d, cache, 2 * d, sb, cache.view(-1)[d:], 2 * d, sb, o, d, B, H, 1, 0.125,
-                          tk_dev=t_dev, tk_max=T_max)
+                          tk_dev=t_dev, tk_max=T_max, k_start=ks)
             self._lin(o, m._w16(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x, res=x)
             # cross attention over the encoder frames
             self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
@@ -297,8 +329,12 @@ class _Decoder:
         self.B, self.Tk = B, Tk
         self.ns_logp = torch.zeros(B, dtype=torch.float32, device=model.device) if track else None
 
-    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None):
+    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False):
         """prompt: int64 [B, P] (device) -> generated ids [B, L] (device), HF trimming.
+        pads: per-row count of leading pad columns of `prompt` (rows left-padded to the longest prompt of the batch,
+        as HF pads them): those columns are masked from the row's self-attention; every row embeds at its column
+        index, as HF does.  shift_positions=True instead counts a row's positions from its first real token, so that
+        it decodes what its unpadded prompt decodes (DecodeSession.set_pads).
         no_speech = (sot_position, token): log-softmax of the raw logits at the <|startoftranscript|>
         position for that token goes to self.ns_logp (WhisperNoSpeechDetection)."""
         sel, P = self.sel, self.P
@@ -307,6 +343,7 @@ class _Decoder:
         else:
             self.sess.set_encoder(enc16)
         sess = self.sess
+        sess.set_pads(pads, shift_positions)
         sel.reset(prompt, temperature, seed)
         sess.t_dev.zero_()
         V = self.m.config.vocab_size
@@ -574,11 +611,40 @@ def retrieve_segment(seq, seek_num_frames, ts_begin=50364, input_stride=2):
     return segs, off
 
 
+# keywords generate implements beyond its named parameters (the fallback settings of HF's long-form generate, the
+# engine's own switches and the tests' private hooks); anything else raises TypeError instead of being dropped
+GENERATE_KEYWORDS = frozenset({"temperature", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
+                               "condition_on_prev_tokens", "do_sample", "seed", "fallback_batch", "_trace", "_keep"})
+
+
 @torch.no_grad()
 def generate(model, input_features=None, max_length=None, num_beams=1, return_timestamps=False, language=None,
              task=None, decoder_input_ids=None, max_new_tokens=None, encoder_outputs=None, attention_mask=None,
-             use_graph=None, **kw):
+             use_graph=None, prompt_ids=None, prompt_condition_type=None, **kw):
+    """HF WhisperGenerationMixin.generate (transformers 5.15 generation_whisper.py), the calls the reference makes.
+    prompt_ids (run_eval.py:656-657 --prompt_text): 1-D ids from get_prompt_ids (<|startofprev|> + text), placed in
+    front of the task prompt of every decoded window (_prepare_decoder_input_ids; with the default
+    prompt_condition_type "first-segment" and no conditioning on previous text, HF puts it in front of each window of a
+    long-form input, not only the first); the begin indices of the suppress / timestamp processors and the length cap
+    count it; the returned ids do not contain it.  Any keyword that is not implemented raises TypeError."""
     from .config import GenerationConfig
+    unknown = sorted(set(kw) - GENERATE_KEYWORDS)
+    if unknown:
+        raise TypeError(f"tw generate: unsupported keyword argument(s) {', '.join(unknown)}")
+    if prompt_condition_type not in (None, "first-segment", "all-segments"):
+        raise ValueError(f"prompt_condition_type={prompt_condition_type!r}: 'first-segment' or 'all-segments'")
+    if prompt_condition_type == "all-segments":
+        raise NotImplementedError("tw generate: prompt_condition_type='all-segments' is not implemented (the prompt "
+                                  "conditions as 'first-segment', HF's default)")
+    if prompt_ids is not None:
+        prompt_ids = [int(t) for t in torch.as_tensor(prompt_ids).reshape(-1).tolist()]
+        if decoder_input_ids is not None:
+            raise ValueError("tw generate: pass prompt_ids or decoder_input_ids, not both")
+        if kw.get("condition_on_prev_tokens"):
+            raise NotImplementedError("tw generate: prompt_ids together with condition_on_prev_tokens is not "
+                                      "implemented")
+        if not prompt_ids:
+            prompt_ids = None
     nb = 1 if num_beams is None else int(num_beams)
     temperature = kw.get("temperature")
     fb = dict(temperature=temperature if temperature is not None else 0.0,
@@ -600,7 +666,7 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     if encoder_outputs is None and input_features is not None and (input_features.shape[-1] > window or seek_loop):
         return _longform(model, gc, input_features, attention_mask, language, task, max_length, max_new_tokens,
                          use_graph, window, kw.get("_trace"), fallback_batch=bool(kw.get("fallback_batch", True)),
-                         num_beams=nb, **fb)
+                         num_beams=nb, prompt_ids=prompt_ids, **fb)
     if kw.get("do_sample") or fb["temperature"] not in (0, 0.0) or fb["logprob_threshold"] is not None \
             or fb["compression_ratio_threshold"] is not None or fb["no_speech_threshold"] is not None:
         # the reference applies fallback / thresholds to long-form inputs only (run_eval.py:659-685)
@@ -620,7 +686,8 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if prompt.dim() == 1:
             prompt = prompt[None].repeat(B, 1)
     else:
-        prompt = torch.tensor(build_prompt(gc, language, task, return_timestamps), dtype=torch.int64)[None].repeat(B, 1)
+        prompt = torch.tensor((prompt_ids or []) + build_prompt(gc, language, task, return_timestamps),
+                              dtype=torch.int64)[None].repeat(B, 1)
     P = prompt.shape[1]
     max_length = total_length(cfg, gc, P, max_length, max_new_tokens)
     if P >= max_length:
@@ -685,9 +752,35 @@ def _bucket(n):
     return b
 
 
+def previous_text(segments, ts_begin):
+    """The tokens of a recording's accepted segments as HF conditions on them (_pad_to_max_length with
+    skip_ending_double_timestamps): a segment that closes on a timestamp pair loses its last timestamp."""
+    prev = []
+    for st in segments:
+        prev.extend(st[:-1] if len(st) > 2 and st[-2] >= ts_begin else st)
+    return prev
+
+
+def conditioned_prompts(init, segments, cond_on, conditioned, prev_sot, cut_off, ts_begin):
+    """The decoder prompts of one seek iteration of the batched long-form loop (HF _prepare_decoder_input_ids):
+    segments / cond_on hold, per active row, its accepted segments and whether it conditions on them.  Not
+    `conditioned`: every row takes init.  Otherwise row r takes <|startofprev|> (prev_sot, when the model has one) +
+    the last cut_off tokens of its previous text (only when cond_on[r] and it has segments) + init.
+    -> (unpadded prompts, the length they are left-padded to)."""
+    if not conditioned:
+        return [list(init) for _ in segments], len(init)
+    head = [int(prev_sot)] if prev_sot is not None else []
+    out = []
+    for sg, on in zip(segments, cond_on):
+        prev = previous_text(sg, ts_begin)[-cut_off:] if on and sg else []
+        out.append(head + prev + list(init))
+    return out, max(len(p) for p in out)
+
+
 def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace, max_length, max_new_tokens,
                       compression_ratio_threshold, logprob_threshold, no_speech_threshold, fallback_batch, decoder, trim,
-                      seeds_of, ns_token, ts_begin, eos, pad, enc_rows=32):
+                      seeds_of, ns_token, ts_begin, eos, pad, enc_rows=32, n_task=None, cond=False, prev_sot=None,
+                      cut_off=None):
     """HF's batched sequential long-form (generation_whisper.py:785-898 with generate_with_fallback :970-1117): every
     recording of the call stays in ONE batch window after window -- each seek iteration cuts the current 30 s window
     of every unfinished recording at its own seek (_get_input_segment, zero-padded), encodes them together, decodes
@@ -702,26 +795,44 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
     while the failing rows are few, several temperature levels of them decode as one batch of at most 8 rows (the
     decode step at <= 8 rows is one GEMV launch per Linear, latency-bound: extra rows are nearly free); each row still
     takes its first passing attempt in temperature order, and a row's attempt decodes the same tokens whichever batch
-    it sits in (per-row temperature and seed, tw_select_sample_ts), so the result is the level-by-level one."""
+    it sits in (per-row temperature and seed, tw_select_sample_ts), so the result is the level-by-level one.
+
+    cond (condition_on_prev_tokens): the recordings stay in one batch too.  At each seek iteration every active row
+    builds its own prompt -- <|startofprev|> + the last cut_off tokens of its accepted segments + the task prompt,
+    conditioned only after a window accepted at temperature < 0.5 -- and the rows are left-padded with pad to the
+    longest prompt of the iteration (HF _prepare_decoder_input_ids / _pad_to_max_length, so HF's length cap, which
+    counts the padded length, is reproduced); the pad columns are masked per row on the device (_Decoder.run pads;
+    passed in every iteration of a conditioned call, all-zero counts included, so a decoder's captured step is not
+    dropped when equal and unequal prompt lengths alternate)
+    and every row embeds at its column index, as transformers 5.15 does (it passes the decoder attention mask but no
+    position ids for Whisper), so a padded row is HF's row, not the decode of its unpadded prompt.
+    As in HF, the conditioned form starts once recording 0 has a segment, and from then on a row without previous
+    text carries <|startofprev|> alone.  init: the unconditioned prompt (prompt_ids + task prompt); n_task: the
+    length of its task part (the <|startoftranscript|> position counts back from the end)."""
     model_cfg = model.config
     dev = model.device
     nmel = feats.shape[1]
     B = feats.shape[0]
     V = model_cfg.vocab_size
-    P = len(init)
-    ml = total_length(model_cfg, gc, P, max_length, max_new_tokens)
-    if P >= ml:
-        raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
-    ns = (0, ns_token) if no_speech_threshold is not None else None
+    n_task = len(init) if n_task is None else n_task
     spec = fallback_batch and batch_rows_independent(model)
     seek = [0] * B
     nwin = [0] * B
     outs = [[] for _ in range(B)]
+    segments = [[] for _ in range(B)]          # accepted segments per recording (the previous text)
+    cond_on = [bool(cond)] * B
     while True:
         active = [b for b in range(B) if seek[b] < int(lens[b])]          # _maybe_reduce_batch
         if not active:
             break
         nfr = {b: min(window, int(lens[b]) - seek[b]) for b in active}
+        prompts, P = conditioned_prompts(init, [segments[b] for b in active], [cond_on[b] for b in active],
+                                         any(cond_on) and len(segments[0]) > 0, prev_sot, cut_off, ts_begin)
+        prompts = dict(zip(active, prompts))
+        ml = total_length(model_cfg, gc, P, max_length, max_new_tokens)
+        if P >= ml:
+            raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
+        ns = (P - n_task, ns_token) if no_speech_threshold is not None else None
         # encode the current windows together (chunks of enc_rows bound the encoder's activations)
         enc = {}
         for c0 in range(0, len(active), enc_rows):
@@ -751,8 +862,11 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
             d_ = decoder(P, ml, nb)
             tl = [temps[f] or 0.0 for _, f in rows_att]
             sl = [seeds[b][f] for b, f in rows_att]
-            raws = d_.run(e16, torch.tensor([init] * nb, dtype=torch.int64, device=dev),
-                          temperature=tl if nb > 1 else tl[0], seed=sl if nb > 1 else sl[0], no_speech=ns).tolist()
+            pads = [P - len(prompts[b]) for b, _ in rows_att]
+            rows_p = [[pad] * n_ + prompts[b] for n_, (b, _) in zip(pads, rows_att)]
+            raws = d_.run(e16, torch.tensor(rows_p, dtype=torch.int64, device=dev),
+                          temperature=tl if nb > 1 else tl[0], seed=sl if nb > 1 else sl[0], no_speech=ns,
+                          **(dict(pads=pads) if cond else {})).tolist()
             del e16
             # a batch is cut at its LAST row's first eos: each row is cut at its own first eos, what its own decode
             # returns
@@ -771,22 +885,23 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
                     needs, skip = need_fallback(cand, avg, nsp, V, compression_ratio_threshold, logprob_threshold,
                                                 no_speech_threshold)
                     if trace is not None:
-                        trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(init), raw=list(raw),
+                        trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(prompts[b]), raw=list(raw),
                                           avg_logprob=avg, no_speech_prob=nsp, needs_fallback=needs, skip=skip,
                                           batch=nb, gate_ms=(time.perf_counter() - tg) * 1e3))
                 elif trace is not None:
-                    trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(init), raw=list(raw),
+                    trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(prompts[b]), raw=list(raw),
                                       batch=nb))
-                result[b] = (raw, skip)
+                result[b] = (raw, skip, temps[f])
                 if not needs:
                     decided.add(b)
             pending = [b for b in pending if b not in decided]
             level = levels[-1] + 1
         del enc
         for b in active:
-            seq, skip = result[b]
+            seq, skip, t_acc = result[b]
             n = nfr[b]
             nwin[b] += 1
+            cond_on[b] = bool(cond) and (t_acc is None or t_acc < 0.5)
             if skip:
                 seek[b] += n
                 continue
@@ -803,6 +918,8 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
             segs, off = retrieve_segment(seq, n, ts_begin)
             for sgm in segs:
                 outs[b].extend(sgm)
+                if cond:
+                    segments[b].append(list(sgm))
             seek[b] += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
     L = max((len(o) for o in outs), default=0)
     res = torch.full((B, L), pad, dtype=torch.int64)
@@ -813,7 +930,8 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
 
 def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
               trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
-              no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1):
+              no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
+              prompt_ids=None):
     """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from
     `seek`; each window decoded with timestamp rules at the first temperature of `temperature` and
     re-decoded at the next one while HF's fallback test fails (compression ratio of the token bytes,
@@ -822,7 +940,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     by the last timestamp (or the whole window on a single-timestamp ending).  With
     condition_on_prev_tokens (and the accepted temperature < 0.5) the next window's prompt is
     <|startofprev|> + the last max_target_positions // 2 - 1 tokens of the clip's segments (a
-    segment's closing timestamp of a double-timestamp ending dropped) + the task prompt.  Returns
+    segment's closing timestamp of a double-timestamp ending dropped) + the task prompt; several
+    recordings still decode as one batch (_longform_batched, rows left-padded to the longest prompt).  Returns
     the concatenated segment tokens, right-padded with pad.  Sampled windows draw from
     softmax(x / T) with the engine's counter-based RNG (seeded by `seed`, the clip, the window and
     the fallback index), not torch's RNG stream.  Once a window's first attempt fails, the remaining
@@ -835,7 +954,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     feats = feats.to(dev, torch.float32)
     B, nmel, T = feats.shape
     lens = attention_mask.sum(-1).tolist() if attention_mask is not None else [T] * B
-    init = build_prompt(gc, language, task, True)
+    task_init = build_prompt(gc, language, task, True)
+    init = list(prompt_ids or []) + task_init      # prompt_ids: in front of every window's task prompt (generate)
     temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (temperature,)
     track = (logprob_threshold is not None or no_speech_threshold is not None or any(t and t > 0 for t in temps)
              or len(temps) > 1)
@@ -877,12 +997,14 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     nbeam = max(1, int(num_beams or 1))
     beam_ts = (ts_begin, int(gc.no_timestamps_token_id), gc.max_initial_timestamp_index
                if "max_initial_timestamp_index" in gc else None)
-    if nbeam == 1 and not condition_on_prev_tokens:
+    if nbeam == 1 and (not condition_on_prev_tokens or B > 1):
         return _longform_batched(model, gc, feats, lens, init, temps, track, window, trace, max_length,
                                  max_new_tokens, compression_ratio_threshold, logprob_threshold, no_speech_threshold,
-                                 fallback_batch, decoder, trim, seeds_of, ns_token, ts_begin, eos, pad)
-    # conditioning on the previous windows' text (per-recording prompts of different lengths: HF left-pads them under
-    # a decoder attention mask) and beam search: one recording at a time
+                                 fallback_batch, decoder, trim, seeds_of, ns_token, ts_begin, eos, pad,
+                                 n_task=len(task_init), cond=bool(condition_on_prev_tokens), prev_sot=prev_sot,
+                                 cut_off=cut_off)
+    # beam search, and conditioning on the previous windows' text for a single recording: one recording at a time
+    # (several conditioned recordings decode as one batch above, their prompts left-padded per row)
     seg_in = torch.zeros(1, nmel, window, dtype=torch.float32, device=dev)
     outs = []
     for b in range(B):
@@ -896,17 +1018,14 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
             enc16 = model.encode(model.conv_input(seg_in))
             prompt = list(init)
             if cond and segments and prev_sot is not None:
-                prev = []
-                for st in segments:
-                    prev.extend(st[:-1] if len(st) > 2 and st[-2] >= ts_begin else st)
-                prompt = [int(prev_sot)] + prev[-cut_off:] + init
+                prompt = [int(prev_sot)] + previous_text(segments, ts_begin)[-cut_off:] + init
             P = len(prompt)
             ml = total_length(cfg, gc, P, max_length, max_new_tokens)
             if P >= ml:
                 raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
             dec = decoder(P, ml)
             ptens = torch.tensor([prompt], dtype=torch.int64, device=dev)
-            ns = (P - len(init), ns_token) if no_speech_threshold is not None else None
+            ns = (P - len(task_init), ns_token) if no_speech_threshold is not None else None
             skip, t_acc, seq = False, temps[0], []
             # attempt fi draws with seed(fi); attempts 1.. run as ONE batch (one row per remaining temperature,
             # speculatively) once attempt 0 fails its gate: a batch-1 decode step is launch-bound, so the

@@ -469,11 +469,15 @@ def gelu_bwd(g, pre, out):
 
 # ----------------------------------------------------------------------------- greedy decode (A12)
 def decode_attn(q, sqb, k, ldk, skb, v, ldv, svb, o, sob, B, H, Tk, scale, tk_dev=None, tk_max=None, hsk=None,
-                hsv=None):
+                hsv=None, k_start=None):
     """One query row per (b, h) over the first Tk (+ *tk_dev) cached key rows (include/tw_hip.h).
     With tk_dev the host cannot know Tk: tk_max bounds the rows checked for extent.  hsk / hsv: head strides of
-    K / V (tw_decode_attn_hs; default 64, heads side by side in a row); skb = svb = 0 shares one clip's K/V."""
+    K / V (tw_decode_attn_hs; default 64, heads side by side in a row); skb = svb = 0 shares one clip's K/V.
+    k_start: device int32 [B], row b attends keys [k_start[b], Tk) only (tw_decode_attn_ks: left-padded prompts)."""
     hd = 64
+    if k_start is not None:
+        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
+        _need(k_start, B, "decode k_start")
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
         assert t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16, torch.float32), nm
     rows = Tk if tk_dev is None else tk_max
@@ -487,6 +491,12 @@ def decode_attn(q, sqb, k, ldk, skb, v, ldv, svb, o, sob, B, H, Tk, scale, tk_de
     # algorithmic bytes (KernelTimer family "decode_attn_cross" / "decode_attn_self"): every K and V
     # element of the rows attended once (self: the host does not know *tk_dev; tk_max bounds it)
     work = 2 * B * rows * H * hd * q.element_size()
+    if k_start is not None:
+        fn = lambda: call("tw_decode_attn_ks", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb,
+                          hv, o.data_ptr(), sob, B, H, Tk, _ptr(tk_dev), k_start.data_ptr(), hd, float(scale), _dt(q),
+                          _stream())
+        KernelTimer.wrap("decode_attn_self_ks" if tk_dev is not None else "decode_attn_cross_ks", work, fn)
+        return o
     if hsk is None and hsv is None:
         fn = lambda: call("tw_decode_attn", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, v.data_ptr(), ldv, svb,
                           o.data_ptr(), sob, B, H, Tk, _ptr(tk_dev), hd, float(scale), _dt(q), _stream())
@@ -600,11 +610,19 @@ def sample_ctl(temperature, seed, out=None):
     return out
 
 
-def embed_step(ids, tok, pos, out, t_dev, max_pos):
+def embed_step(ids, tok, pos, out, t_dev, max_pos, pos_off=None):
+    """out[b] = tok[ids[b]] + pos[*t_dev]; with pos_off (device int32 [B], each row's left-pad count):
+    pos[max(*t_dev - pos_off[b], 0)] (tw_embed_step_off)."""
     B = ids.numel()
     D = tok.shape[1]
     assert ids.dtype == torch.int64 and t_dev.dtype == torch.int32 and out.numel() == B * D
     assert pos.shape[0] >= max_pos
+    if pos_off is not None:
+        assert pos_off.dtype == torch.int32 and pos_off.is_contiguous() and pos_off.device == out.device
+        _need(pos_off, B, "embed_step pos_off")
+        call("tw_embed_step_off", ids.data_ptr(), tok.data_ptr(), _dt(tok), pos.data_ptr(), _dt(pos), out.data_ptr(),
+             _dt(out), B, D, t_dev.data_ptr(), pos_off.data_ptr(), _stream())
+        return out
     call("tw_embed_step", ids.data_ptr(), tok.data_ptr(), _dt(tok), pos.data_ptr(), _dt(pos), out.data_ptr(),
          _dt(out), B, D, t_dev.data_ptr(), _stream())
     return out
