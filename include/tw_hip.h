@@ -230,6 +230,47 @@ int tw_decode_attn_hs(const void* q, int64_t sqb, const void* k, int64_t ldk, in
 int tw_decode_attn_ks(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
                       const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B, int H, int Tk,
                       const int* tk_dev, const int* k_start, int head_dim, float scale, int dtype, tw_stream_t stream);
+/* tw_decode_attn_mq: tw_decode_attn_ks for Q consecutive query rows per batch row (1 <= Q <= 8) -- the verify pass
+ * of assisted decoding (HF generate(assistant_model=...), run_eval.py:524-545,653-654), where the target scores
+ * the k drafted tokens and the one before them in one pass.  Query j of row b is at q + b*sqb + j*sqq + h*64, its
+ * output at o + b*sob + j*soq + h*64, and it attends keys [k_start[b], Tk + (causal ? j : 0)) (Tk += *tk_dev as
+ * above; k_start may be NULL: every start 0; a start at or past a query's limit is clamped for that query as
+ * tw_decode_attn_ks clamps it).  Every K and every V row is loaded once and used for all Q queries, so the 1500-frame
+ * cross-attention K/V of a round is read once, not Q times; rows at or above the last query's limit and below the
+ * start are never loaded.  Per query the arithmetic is that of the single-query body: the same lane layout, key
+ * order, two-pass max / sum, the same split rule (fixed Tk and fewer than 640 (row, head) pairs, counted as for one
+ * step; the chunk count from the last query's limit) and combine order, so query j's output is bit-identical to
+ * tw_decode_attn_ks on that query alone with Tk + (causal ? j : 0) keys (for a causal call with a fixed Tk: when
+ * every query falls on the same side of the split rule).  The one-workgroup path keeps the scores of the Q queries
+ * in 48 KB of LDS: at most 12288 / Q' keys per query (Q' = Q rounded up to 1, 2, 4, 8; 1536 at Q = 8) -- a fixed Tk
+ * beyond that returns 2, a device-side one is cut there.  4096 (row, head) pairs or more return 2.  bf16, fp16, fp32. */
+int tw_decode_attn_mq(const void* q, int64_t sqb, int64_t sqq, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
+                      const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int64_t soq, int B,
+                      int H, int Q, int Tk, const int* tk_dev, const int* k_start, int causal, int head_dim,
+                      float scale, int dtype, tw_stream_t stream);
+/* tw_spec_accept: acceptance and rollback of one round of assisted decoding, one row, on the device (nothing is
+ * synchronised with the host).  Before the call: *t_dev = t, the column of the last accepted token; drafts[0..k) the
+ * assistant's tokens for columns t+1 .. t+k; ids[t+1 .. t+k+1] the target's tokens (the selection kernels, one launch
+ * per logit row of the verify pass); slots[0..k] the log-prob each of those launches added to its own zeroed slot
+ * (NULL together with sum_logp when nothing is tracked); done_snap the row's finished flag as it was before the
+ * round.  n = the number of leading drafts equal to the target's token at the same column, counted up to and
+ * including the first eos; the accepted tokens are the n + 1 target tokens at t+1 .. t+n+1, cut at column t_cap - 1
+ * (the length cap: ids, the caches and the position lookups need k + 1 spare columns / rows past it).  The kernel
+ * refills ids past the last accepted column (up to t+k+1) with eos, sets cur (and cur_a) to the last accepted token,
+ * *t_dev (and *t_dev_a) to its column, done (done_a, and done_snap for the next round) from the snapshot and the
+ * accepted tokens, last_ts (last_ts_a; NULL without timestamps) to the last token >= ts_begin among columns
+ * begin_col .. the last accepted one (-1: none), adds the accepted slots to sum_logp in position order -- the
+ * sequential decode's fp32 additions -- and zeroes the slots.  hist (nullable): hist[0] counts the rounds,
+ * hist[1 + r] = n of round r while 1 + r < hist_cap.  A round that starts finished or at the length cap changes
+ * nothing but the eos refill. */
+int tw_spec_accept(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev, int* t_dev_a,
+                   int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a, uint8_t* done_snap, int* last_ts,
+                   int* last_ts_a, int begin_col, int ts_begin, float* slots, float* sum_logp, int* hist,
+                   int hist_cap, tw_stream_t stream);
+/* tw_embed_step_multi: out[j] = tok[ids[j]] + pos[min(*t_dev + j, npos - 1)] for the Q consecutive positions of
+ * one row (the verify pass; Q = 1: a step whose position is clamped to the table). */
+int tw_embed_step_multi(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
+                        int out_dtype, int Q, int D, const int* t_dev, int npos, tw_stream_t stream);
 int tw_greedy_select(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
                      const uint32_t* begin_bits, int apply_begin, int64_t eos, uint8_t* done, int64_t* ids,
                      int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col, tw_stream_t stream);

@@ -120,6 +120,186 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_split_ks_kernel(DecP p
   decode_attn_body<E>(p, b, h, lo, hi, part);
 }
 
+// Multi-query decode attention (tw_decode_attn_mq: the verify pass of assisted decoding).  nq <= QN query rows per
+// (clip, head); query j attends keys [start_j, tk_j), tk_j = Tk (+ *tk_dev) (+ j when causal), start_j the row's
+// k_start clamped into [0, tk_j - 1] as tw_decode_attn_ks clamps it.  The queries that share a start -- all of them
+// unless the start reaches a query's limit -- go through decode_attn_body_mq together (each K / V row loaded once);
+// a query whose clamped start differs walks the keys from its own start, as its single-query call does, in a
+// pass of its own.
+struct MqP {
+  int64_t sqq, soq;
+  int nq, causal;
+  const int* k_start;
+};
+template <int QN>
+__device__ __forceinline__ void mq_group(unsigned& pend, const int (&lo)[QN], const int (&hi)[QN], int& glo,
+                                         int (&ghi)[QN]) {
+  bool found = false;
+  glo = 0;
+#pragma unroll
+  for (int j = 0; j < QN; ++j)
+    if (!found && ((pend >> j) & 1u)) { glo = lo[j]; found = true; }
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    const bool in = ((pend >> j) & 1u) && lo[j] == glo;
+    ghi[j] = in ? hi[j] : glo;
+    if (in) pend &= ~(1u << j);
+  }
+}
+template <typename E, int QN>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_kernel(DecP p, MqP q) {
+  __shared__ float sc[DA_MQ_LDS];
+  constexpr int cap = DA_MQ_LDS / QN > DA_MAX_TK ? DA_MAX_TK : DA_MQ_LDS / QN;
+  const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
+  const int tk0 = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+  int lo[QN], hi[QN];
+  unsigned pend = 0;
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    lo[j] = hi[j] = 0;
+    if (j < q.nq) {
+      const int tk = min(tk0 + (q.causal ? j : 0), DA_MAX_TK);
+      lo[j] = q.k_start ? clamp_start(q.k_start, b, tk) : 0;
+      hi[j] = min(tk, lo[j] + cap);
+      if (hi[j] > lo[j]) pend |= 1u << j;
+    }
+  }
+  while (pend) {
+    int glo, ghi[QN];
+    mq_group<QN>(pend, lo, hi, glo, ghi);
+    decode_attn_body_mq<E, QN, 4, true>(p, q.sqq, q.soq, b, h, glo, ghi, sc, cap, nullptr, 0);
+    if (pend) __syncthreads();
+  }
+}
+
+// split over keys: blockIdx.y = chunk of DA_SPLIT keys; query j's partials at ws + ((bh * nq + j) * nchunk + c) * 66
+template <typename E, int QN>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_split_kernel(DecP p, MqP q, float* ws) {
+  __shared__ float sc[QN * DA_SPLIT];
+  const int bh = blockIdx.x, c = blockIdx.y, nchunk = gridDim.y;
+  const int b = bh / p.H, h = bh % p.H;
+  float* part = ws + (((int64_t)bh * q.nq) * nchunk + c) * 66;
+  const int64_t pstride = (int64_t)nchunk * 66;
+  int lo[QN], hi[QN];
+  unsigned pend = 0;
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    lo[j] = hi[j] = 0;
+    if (j < q.nq) {
+      const int tk = min(p.Tk + (q.causal ? j : 0), DA_MAX_TK);
+      lo[j] = max(c * DA_SPLIT, q.k_start ? clamp_start(q.k_start, b, tk) : 0);
+      hi[j] = min(tk, c * DA_SPLIT + DA_SPLIT);
+      if (hi[j] > lo[j]) {
+        pend |= 1u << j;
+      } else {                                           // chunk past the query's keys or below its start: empty
+        float* pj = part + j * pstride;
+        if (threadIdx.x < 64) pj[threadIdx.x] = 0.f;
+        if (threadIdx.x == 0) {
+          pj[64] = -INFINITY;
+          pj[65] = 0.f;
+        }
+      }
+    }
+  }
+  while (pend) {
+    int glo, ghi[QN];
+    mq_group<QN>(pend, lo, hi, glo, ghi);
+    decode_attn_body_mq<E, QN>(p, q.sqq, q.soq, b, h, glo, ghi, sc, DA_SPLIT, part, pstride);
+    if (pend) __syncthreads();
+  }
+}
+
+template <typename E>
+__global__ __launch_bounds__(64) void decode_attn_mq_combine_kernel(DecP p, MqP q, int nchunk, const float* ws) {
+  const int j = blockIdx.x % q.nq, bh = blockIdx.x / q.nq;
+  p.o = (E*)p.o + j * q.soq;
+  combine_row<E>(p, bh, nchunk, ws + (int64_t)blockIdx.x * nchunk * 66);
+}
+
+// Acceptance and rollback of one round of assisted decoding, one row, one wave (tw_spec_accept in tw_hip.h).
+struct AccP {
+  const int64_t* drafts; int k;
+  int64_t* ids; int t_cap; int64_t eos;
+  int* t_dev; int* t_dev_a;
+  int64_t* cur; int64_t* cur_a;
+  uint8_t* done; uint8_t* done_a; uint8_t* done_snap;
+  int* last_ts; int* last_ts_a; int begin_col, ts_begin;
+  float* slots; float* sum_logp;
+  int* hist; int hist_cap;
+};
+__global__ __launch_bounds__(64) void spec_accept_kernel(AccP a) {
+  const int lane = threadIdx.x;
+  const int t = *a.t_dev;
+  const bool was_done = a.done_snap[0] != 0;
+  const bool frozen = was_done || t + 1 >= a.t_cap;
+  // n: leading drafts equal to the target's token at the same column, counted up to and including the first eos
+  int n = 0;
+  for (int j = 0; j < a.k; ++j) {
+    const int64_t g = a.ids[t + 1 + j];
+    if (g != a.drafts[j]) break;
+    ++n;
+    if (g == a.eos) break;
+  }
+  const int adv = frozen ? 0 : min(n + 1, a.t_cap - 1 - t);     // accepted target tokens: columns t+1 .. t+adv
+  bool fin = was_done;
+  for (int j = 1; j <= adv; ++j) fin = fin || a.ids[t + j] == a.eos;
+  const int64_t cur = a.ids[t + adv];
+  float s = 0.f;
+  if (a.sum_logp) {
+    s = a.sum_logp[0];
+    for (int j = 0; j < adv; ++j) s += a.slots[j];              // position order: the sequential decode's additions
+  }
+  // last timestamp among the accepted generated columns [begin_col, t + adv], scanned backwards 64 columns a step
+  int lts = -1;
+  if (a.last_ts) {
+    for (int c0 = t + adv; c0 >= a.begin_col; c0 -= 64) {
+      const int c = c0 - lane;
+      const bool is_ts = c >= a.begin_col && a.ids[c] >= a.ts_begin;
+      const unsigned long long hit = __ballot(is_ts);
+      if (hit) {
+        lts = (int)a.ids[c0 - (__ffsll((long long)hit) - 1)];
+        break;
+      }
+    }
+  }
+  __syncthreads();                                              // every read above precedes the stores below
+  if (lane > adv && lane <= a.k + 1) a.ids[t + lane] = a.eos;   // columns past t + adv back to the eos fill
+  if (a.slots && lane <= a.k) a.slots[lane] = 0.f;
+  if (lane != 0) return;
+  *a.t_dev = t + adv;
+  if (a.t_dev_a) *a.t_dev_a = t + adv;
+  a.cur[0] = cur;
+  if (a.cur_a) a.cur_a[0] = cur;
+  const uint8_t d = fin ? 1 : 0;
+  a.done[0] = d;
+  a.done_snap[0] = d;
+  if (a.done_a) a.done_a[0] = d;
+  if (a.last_ts) {
+    a.last_ts[0] = lts;
+    if (a.last_ts_a) a.last_ts_a[0] = lts;
+  }
+  if (a.sum_logp) a.sum_logp[0] = s;
+  if (a.hist && !frozen) {
+    const int r = a.hist[0];
+    if (r + 1 < a.hist_cap) a.hist[1 + r] = n;
+    a.hist[0] = r + 1;
+  }
+}
+
+// x[j] = tok[ids[j]] + pos[min(*t_dev + j, npos - 1)]: the Q consecutive positions of one row's verify pass (a round
+// that reaches past the last position embeds its surplus rows at the last one; their tokens are discarded)
+__global__ void embed_step_multi_kernel(const int64_t* __restrict__ ids, const void* __restrict__ tok, int tok_dtype,
+                                        const void* __restrict__ pos, int pos_dtype, void* __restrict__ out,
+                                        int out_dtype, int D, const int* __restrict__ t_dev, int npos) {
+  const int j = blockIdx.x;
+  const int64_t id = ids[j];
+  const int64_t t = min(*t_dev + j, npos - 1);
+  for (int e = threadIdx.x; e < D; e += blockDim.x) {
+    const float s = ld_as_f32(tok, tok_dtype, id * D + e) + ld_as_f32(pos, pos_dtype, t * D + e);
+    st_from_f32(out, out_dtype, (int64_t)j * D + e, s);
+  }
+}
+
 struct SelP {
   const void* logits; int64_t ld;
   int V;
@@ -861,6 +1041,104 @@ extern "C" int tw_decode_attn_ks(const void* q, int64_t sqb, const void* k, int6
   }
   if (B * H >= DA_BIG) TW_LAUNCH_DT(dtype, decode_attn_ks_u2_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
   else TW_LAUNCH_DT(dtype, decode_attn_ks_u4_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+namespace {
+template <int QN>
+int launch_mq(const DecP& p, const MqP& q, int B, int nchunk, bool split, int dtype, hipStream_t stream) {
+  if (split) {
+    float* ws = (float*)tw_device_workspace(stream, (size_t)B * p.H * q.nq * nchunk * 66 * sizeof(float));
+    if (ws) {
+      if (dtype == TW_BF16) {
+        hipLaunchKernelGGL((decode_attn_mq_split_kernel<bf16, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
+        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<bf16>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
+      } else if (dtype == TW_F16) {
+        hipLaunchKernelGGL((decode_attn_mq_split_kernel<f16, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
+        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<f16>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
+      } else {
+        hipLaunchKernelGGL((decode_attn_mq_split_kernel<float, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
+        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<float>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
+      }
+      TW_CHECK_LAUNCH();
+      return TW_OK;
+    }
+  }
+  if (dtype == TW_BF16)
+    hipLaunchKernelGGL((decode_attn_mq_kernel<bf16, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
+  else if (dtype == TW_F16)
+    hipLaunchKernelGGL((decode_attn_mq_kernel<f16, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
+  else
+    hipLaunchKernelGGL((decode_attn_mq_kernel<float, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+}  // namespace
+
+// tw_decode_attn_ks for Q consecutive query rows per batch row: the same argument checks, the same split rule (the
+// (row, head) pairs counted as for one step, the chunks from the last query's key count), the same bodies per query
+extern "C" int tw_decode_attn_mq(const void* q, int64_t sqb, int64_t sqq, const void* k, int64_t ldk, int64_t skb,
+                                 int64_t hsk, const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o,
+                                 int64_t sob, int64_t soq, int B, int H, int Q, int Tk, const int* tk_dev,
+                                 const int* k_start, int causal, int head_dim, float scale, int dtype,
+                                 hipStream_t stream) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (Q < 1 || Q > DA_MQ) return TW_EINVAL;
+  if (B <= 0 || H <= 0) return TW_OK;
+  if (dtype != TW_BF16 && dtype != TW_F16 && dtype != TW_F32) return TW_EUNSUPPORTED;
+  const int tk_last = Tk + (causal ? Q - 1 : 0);
+  if ((!tk_dev && Tk <= 0) || tk_last > DA_MAX_TK || B * H >= DA_BIG) return TW_EUNSUPPORTED;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
+  if ((sqb | sqq | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
+  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0 || sqq < 0 || soq < 0) return TW_EINVAL;
+  const int QN = Q <= 1 ? 1 : Q <= 2 ? 2 : Q <= 4 ? 4 : 8;
+  const int nchunk = (tk_last + DA_SPLIT - 1) / DA_SPLIT;
+  const bool split = !tk_dev && B * H < 640 && nchunk >= 2 && nchunk <= DA_MAX_CHUNK;
+  // one-workgroup path: a query's scores live in DA_MQ_LDS / QN floats of LDS
+  if (!split && !tk_dev && tk_last > DA_MQ_LDS / QN) return TW_EUNSUPPORTED;
+  DecP p;
+  p.q = q; p.sqb = sqb;
+  p.k = k; p.ldk = ldk; p.skb = skb;
+  p.v = v; p.ldv = ldv; p.svb = svb;
+  p.o = o; p.sob = sob;
+  p.hsk = hsk; p.hsv = hsv;
+  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.c = scale * 1.4426950408889634f;
+  MqP m;
+  m.sqq = sqq; m.soq = soq; m.nq = Q; m.causal = causal ? 1 : 0; m.k_start = k_start;
+  switch (QN) {
+    case 1: return launch_mq<1>(p, m, B, nchunk, split, dtype, stream);
+    case 2: return launch_mq<2>(p, m, B, nchunk, split, dtype, stream);
+    case 4: return launch_mq<4>(p, m, B, nchunk, split, dtype, stream);
+    default: return launch_mq<8>(p, m, B, nchunk, split, dtype, stream);
+  }
+}
+
+extern "C" int tw_spec_accept(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev,
+                              int* t_dev_a, int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a,
+                              uint8_t* done_snap, int* last_ts, int* last_ts_a, int begin_col, int ts_begin,
+                              float* slots, float* sum_logp, int* hist, int hist_cap, hipStream_t stream) {
+  if (k < 1 || k >= DA_MQ || !drafts || !ids || !t_dev || !cur || !done || !done_snap || t_cap < 1 || begin_col < 0)
+    return TW_EINVAL;
+  if ((sum_logp != nullptr) != (slots != nullptr) || (hist && hist_cap < 1)) return TW_EINVAL;
+  AccP a;
+  a.drafts = drafts; a.k = k; a.ids = ids; a.t_cap = t_cap; a.eos = eos;
+  a.t_dev = t_dev; a.t_dev_a = t_dev_a; a.cur = cur; a.cur_a = cur_a;
+  a.done = done; a.done_a = done_a; a.done_snap = done_snap;
+  a.last_ts = last_ts; a.last_ts_a = last_ts_a; a.begin_col = begin_col; a.ts_begin = ts_begin;
+  a.slots = slots; a.sum_logp = sum_logp; a.hist = hist; a.hist_cap = hist_cap;
+  hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, stream, a);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+extern "C" int tw_embed_step_multi(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype,
+                                   void* out, int out_dtype, int Q, int D, const int* t_dev, int npos,
+                                   hipStream_t stream) {
+  if (Q <= 0) return TW_OK;
+  if (!t_dev || D <= 0 || npos < 1) return TW_EINVAL;
+  hipLaunchKernelGGL(embed_step_multi_kernel, dim3(Q), dim3(256), 0, stream, ids, tok, tok_dtype, pos, pos_dtype, out,
+                     out_dtype, D, t_dev, npos);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }

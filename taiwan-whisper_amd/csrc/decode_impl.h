@@ -147,6 +147,152 @@ __device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, in
   }
 }
 
+// Multi-query form of decode_attn_body (the verify pass of assisted decoding: QN consecutive query rows of one
+// (clip, head), rows sqq apart, outputs soq apart): every K and every V vector is loaded ONCE and used for all the
+// queries.  Query j attends keys [lo, hi[j]) -- one common lo, which fixes the key -> (wave, sub-step, lane slot)
+// walk, so per query every operation below is the one decode_attn_body performs for that query alone, in the same
+// order: the outputs are bit-identical.  hi[j] <= lo leaves query j out (nothing computed or stored for it).
+// Keys at or above max_j hi[j] are never loaded.  sc: LDS scores, QN rows of `cap` floats (hi[j] - lo <= cap).
+// part == nullptr: normalise and store O; otherwise query j's partial goes to part + j * pstride (66 floats).
+constexpr int DA_MQ = 8;                // most query rows per (clip, head)
+constexpr int DA_MQ_LDS = 12288;        // score floats of the one-workgroup multi-query kernel (48 KB)
+template <typename E, int QN, int DA_U = twd::DA_U, bool NT = false>
+__device__ __forceinline__ void decode_attn_body_mq(const DecP& p, int64_t sqq, int64_t soq, int b, int h, int lo,
+                                                    const int (&hi)[QN], float* sc, int cap, float* part,
+                                                    int64_t pstride) {
+  __shared__ float red[DA_THREADS / 64][QN][64];
+  __shared__ float red_l[DA_THREADS / 64][QN];
+  __shared__ float red_m[DA_THREADS / 64][QN];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ks = lane >> 3, ch = lane & 7;
+  constexpr bool F32 = sizeof(E) == 4;
+  const E* qb = (const E*)p.q + b * p.sqb + h * 64 + ch * 8;
+  const E* kb = (const E*)p.k + b * p.skb + h * p.hsk + ch * 8;
+  const E* vb = (const E*)p.v + b * p.svb + h * p.hsv + ch * 8;
+  int himax = lo;
+#pragma unroll
+  for (int j = 0; j < QN; ++j) himax = max(himax, hi[j]);
+  float qv[QN][8];
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    if (hi[j] > lo) {
+      load8(qb + j * sqq, qv[j]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) qv[j][i] = 0.f;
+    }
+  }
+  // pass 1: one K load per key, QN scores
+  float mx[QN];
+#pragma unroll
+  for (int j = 0; j < QN; ++j) mx[j] = -INFINITY;
+  for (int k0 = lo + wave * 8 * DA_U; k0 < himax; k0 += DA_THREADS / 8 * DA_U) {
+    float t[DA_U][8];
+#pragma unroll
+    for (int u = 0; u < DA_U; ++u) {
+      const int key = k0 + 8 * u + ks;
+      if (key < himax) load8_kv<NT>(kb + (int64_t)key * p.ldk, t[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < DA_U; ++u) {
+      const int key = k0 + 8 * u + ks;
+#pragma unroll
+      for (int j = 0; j < QN; ++j) {
+        if (k0 + 8 * u >= hi[j]) continue;             // uniform: none of this sub-step's keys is query j's
+        float sv = 0.f;
+        if (key < hi[j]) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) sv = fmaf(qv[j][i], t[u][i], sv);
+        }
+        sv = oct_sum_dpp(sv);
+        if (key < hi[j]) {
+          sv *= p.c;
+          if (ch == 0) sc[j * cap + key - lo] = sv;
+          mx[j] = fmaxf(mx[j], sv);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    mx[j] = wave_max_dpp(mx[j]);
+    if (lane == 0) red_m[wave][j] = mx[j];
+  }
+  __syncthreads();
+  float m[QN];
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    m[j] = red_m[0][j];
+#pragma unroll
+    for (int w = 1; w < DA_THREADS / 64; ++w) m[j] = fmaxf(m[j], red_m[w][j]);
+  }
+  // pass 2: one V load per key, QN weighted sums
+  float o[QN][8];
+  float l[QN];
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    l[j] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[j][i] = 0.f;
+  }
+  for (int k0 = lo + wave * 8 * DA_U; k0 < himax; k0 += DA_THREADS / 8 * DA_U) {
+    float t[DA_U][8];
+#pragma unroll
+    for (int u = 0; u < DA_U; ++u) {
+      const int key = k0 + 8 * u + ks;
+      if (key < himax) load8_kv<NT>(vb + (int64_t)key * p.ldv, t[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < DA_U; ++u) {
+      const int key = k0 + 8 * u + ks;
+#pragma unroll
+      for (int j = 0; j < QN; ++j) {
+        if (key < hi[j]) {
+          const float s = sc[j * cap + key - lo];
+          const float pe = F32 ? exp2f(s - m[j]) : __builtin_amdgcn_exp2f(s - m[j]);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o[j][i] = fmaf(pe, t[u][i], o[j][i]);
+          if (ch == 0) l[j] += pe;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[j][i] = stride8_sum_dpp(o[j][i]);
+    l[j] = wave_sum_dpp(l[j]);
+    if (ks == 0) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) red[wave][j][ch * 8 + i] = o[j][i];
+    }
+    if (lane == 0) red_l[wave][j] = l[j];
+  }
+  __syncthreads();
+  if (tid < 64) {
+#pragma unroll
+    for (int j = 0; j < QN; ++j) {
+      if (hi[j] <= lo) continue;
+      float acc = 0.f, lt = 0.f;
+#pragma unroll
+      for (int w = 0; w < DA_THREADS / 64; ++w) {
+        acc += red[w][j][tid];
+        lt += red_l[w][j];
+      }
+      if (part) {
+        float* pj = part + j * pstride;
+        pj[tid] = acc;
+        if (tid == 0) {
+          pj[64] = m[j];
+          pj[65] = lt;
+        }
+      } else {
+        ((E*)p.o)[b * p.sob + j * soq + h * 64 + tid] = e_from_f32<E>(acc / lt);
+      }
+    }
+  }
+}
+
 // O = sum_c 2^(m_c - M) o_c / sum_c 2^(m_c - M) l_c over the chunks of one (clip, head), in chunk order,
 // by the 64 lanes of one wave (lane = output dimension).  Lane c loads chunk c's (m, l) and every lane its
 // column of all chunks up front (independent loads instead of a dependent chain), weights by shuffles.

@@ -59,6 +59,11 @@ SIGNATURES = {
     "tw_decode_attn": [P, I64, P, I64, I64, P, I64, I64, P, I64, I32, I32, I32, P, I32, F32, I32, P],
     "tw_decode_attn_hs": [P, I64, P, I64, I64, I64, P, I64, I64, I64, P, I64, I32, I32, I32, P, I32, F32, I32, P],
     "tw_decode_attn_ks": [P, I64, P, I64, I64, I64, P, I64, I64, I64, P, I64, I32, I32, I32, P, P, I32, F32, I32, P],
+    # assisted decoding: multi-query decode attention, acceptance / rollback, the verify pass's embedding
+    "tw_decode_attn_mq": [P, I64, I64, P, I64, I64, I64, P, I64, I64, I64, P, I64, I64, I32, I32, I32, I32, P, P, I32,
+                          I32, F32, I32, P],
+    "tw_spec_accept": [P, I32, P, I32, I64, P, P, P, P, P, P, P, P, P, I32, I32, P, P, P, I32, P],
+    "tw_embed_step_multi": [P, P, I32, P, I32, P, I32, I32, I32, P, I32, P],
     "tw_embed_step_off": [P, P, I32, P, I32, P, I32, I32, I32, P, P, P],
     "tw_greedy_select": [P, I64, I32, I32, I32, P, P, I32, I64, P, P, I64, I32, P, P, I32, P],
     "tw_greedy_select_ts": [P, I64, I32, I32, I32, P, P, I64, P, P, I64, I32, P, P, I32, I32, I32, I32, P, P],

@@ -37,9 +37,14 @@ class DecodeSession:
     """Device state of one greedy decode over a batch; every step is position-independent (the step
     index lives in `t_dev`), so the whole step is captured once into a HIP graph and replayed."""
 
-    def __init__(self, model, enc16: torch.Tensor, B: int, Tk: int, T_max: int):
+    def __init__(self, model, enc16: torch.Tensor, B: int, Tk: int, T_max: int, spare: int = 0):
+        """spare: cache rows past T_max for the rounds of assisted decoding (step_multi writes Q rows at once, so a
+        round that starts at the last position stays inside the caches); the positions then clamp to the table."""
         cfg = model.config
+        T_max = T_max + spare
         self.m, self.B, self.Tk, self.T_max = model, B, Tk, T_max
+        self.clamp_pos = spare > 0
+        self.mq = None                   # buffers of step_multi (alloc_multi)
         self.d = cfg.d_model
         self.H = self.d // 64
         dev = model.device
@@ -142,12 +147,13 @@ class DecodeSession:
             self.k_start.copy_(v)
             self.pos_off.copy_(v)
 
-    def _ln(self, x, name):
+    def _ln(self, x, name, y=None):
         m = self.m
-        F.layernorm_fwd(x, m.ln_param(name + ".weight"), m.ln_param(name + ".bias"), self.y)
-        return self.y
+        y = self.y if y is None else y
+        F.layernorm_fwd(x, m.ln_param(name + ".weight"), m.ln_param(name + ".bias"), y)
+        return y
 
-    def _ln_lin(self, x, ln, w, b, out, flags=F.GEMM_ROUND, kv=None):
+    def _ln_lin(self, x, ln, w, b, out, flags=F.GEMM_ROUND, kv=None, y=None):
         """out = Linear(LayerNorm(x)): one GEMV launch (batch <= 4, bf16 stream) or LN + GEMM.  kv: the
         GEMV also appends columns >= kv[3] to the self-attention cache row (only on the GEMV path)."""
         m = self.m
@@ -155,7 +161,7 @@ class DecodeSession:
             F.gemv(x, w, out, ln_w=m.ln_param(ln + ".weight"), ln_b=m.ln_param(ln + ".bias"), bias=b, flags=flags,
                    kv=kv)
         else:
-            y = self._ln(x, ln)
+            y = self._ln(x, ln, y)
             if self.gemv:
                 F.gemv(y, w, out, bias=b, flags=flags)
             else:
@@ -169,17 +175,93 @@ class DecodeSession:
             self.m._lin(a, w, b, out, res=res, flags=flags)
         return out
 
-    def step(self, select=None):
-        """One decoder step at position *t_dev for input ids `cur`; then t_dev += 1.
-        select = (sup, beg, eos, done, ids, P) runs greedy selection into ids[:, t+1] and cur."""
-        m, B, d, H, T_max = self.m, self.B, self.d, self.H, self.T_max
+    def _embed_tables(self):
+        m = self.m
         if m.store.p32 is not None:
-            E, Pe = m.store.v32("model.decoder.embed_tokens.weight"), m.store.v32("model.decoder.embed_positions.weight")
+            return m.store.v32("model.decoder.embed_tokens.weight"), m.store.v32("model.decoder.embed_positions.weight")
+        return m.store.v16("model.decoder.embed_tokens.weight"), m.store.v16("model.decoder.embed_positions.weight")
+
+    def alloc_multi(self, Q):
+        """Activation buffers of step_multi: Q rows each (one row of the batch, Q consecutive positions)."""
+        m, d, dev, act = self.m, self.d, self.m.device, self.m.act_dtype
+        assert self.B == 1 and 1 <= Q <= F.MQ_MAX
+        if self.mq is None or self.mq["Q"] != Q:
+            self.mq = dict(Q=Q, x=torch.empty(Q, d, dtype=m.stream_dtype, device=dev),
+                           y=torch.empty(Q, d, dtype=act, device=dev), qkv=torch.empty(Q, 3 * d, dtype=act, device=dev),
+                           o=torch.empty(Q, d, dtype=act, device=dev), q=torch.empty(Q, d, dtype=act, device=dev),
+                           h=torch.empty(Q, m.config.decoder_ffn_dim, dtype=act, device=dev),
+                           logits=torch.empty(Q, m.Vp, dtype=act, device=dev))
+        return self.mq
+
+    def step_multi(self, Q, ids, select=None):
+        """The forward of ONE row for the Q tokens ids[0..Q) at positions *t_dev .. *t_dev + Q - 1 (the verify pass
+        of assisted decoding): the step's launches with M = Q rows -- the Linears read each weight once for the Q
+        rows (the GEMV at d % 256 == 0 on the 16-bit paths, else the GEMM; a row of either does not depend on M) --
+        K/V of the Q positions to cache rows t .. t+Q-1, self-attention causal among the Q rows and cross-attention
+        through tw_decode_attn_mq (each K / V row loaded once for the Q queries; per query the single-query
+        arithmetic), Q logit rows.  Position-independent (t read on the device); t_dev is NOT advanced: the caller
+        decides how many positions stand (tw_spec_accept).  select(self, logits) runs after the head."""
+        m, d, H, T_max = self.m, self.d, self.H, self.T_max
+        assert self.B == 1 and not self.padded and self.spare_ok(Q)
+        b = self.alloc_multi(Q)
+        x, o, t_dev = b["x"], b["o"], self.t_dev
+        E, Pe = self._embed_tables()
+        F.embed_step_multi(ids, E, Pe, x, t_dev, Q)
+        rows = T_max - (Q - 1)                   # the first of the Q cache rows written is below this
+        for i in range(m.config.decoder_layers):
+            p = f"model.decoder.layers.{i}"
+            wqkv = m.wspan(p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d))
+            bqkv = m.wspan(p + ".self_attn.q_proj.bias", p + ".self_attn.v_proj.bias", (3 * d,))
+            cache = self.self_kv[i]
+            if self.gemv_ln:        # row j of the GEMV goes to cache row t + j: batch stride = row stride
+                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b["qkv"], kv=(cache, 2 * d, 2 * d, d, t_dev,
+                                                                                     rows), y=b["y"])
+            else:
+                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b["qkv"], y=b["y"])
+                F.kv_append(b["qkv"][:, d:], 3 * d, cache, 2 * d, 2 * d, Q, 2 * d, t_dev, rows)
+            F.decode_attn_mq(b["qkv"], Q * 3 * d, 3 * d, cache, 2 * d, 0, cache.view(-1)[d:], 2 * d, 0, o, Q * d, d,
+                             1, H, Q, 1, 0.125, tk_dev=t_dev, tk_max=T_max, causal=True)
+            self._lin(o, m._w16(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x, res=x)
+            self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
+                         m._w16(p + ".encoder_attn.q_proj.bias"), b["q"], y=b["y"])
+            kv = self.cross_kv[i]
+            if self.hm:             # the clip's [H][Tk][64] K then V blocks
+                n1 = H * self.Tk * 64
+                F.decode_attn_mq(b["q"], Q * d, d, kv, 64, 0, kv[n1:], 64, 0, o, Q * d, d, 1, H, Q, self.Tk, 0.125,
+                                 hsk=self.Tk * 64, hsv=self.Tk * 64)
+            else:
+                F.decode_attn_mq(b["q"], Q * d, d, kv, 2 * d, 0, kv[:, d:], 2 * d, 0, o, Q * d, d, 1, H, Q, self.Tk,
+                                 0.125)
+            self._lin(o, m._w16(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"), x,
+                      res=x)
+            self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), b["h"],
+                         flags=F.GEMM_ROUND | F.GEMM_GELU, y=b["y"])
+            self._lin(b["h"], m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
+        if self.gemv_ln:
+            self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None,
+                         b["logits"], y=b["y"])
         else:
-            E, Pe = m.store.v16("model.decoder.embed_tokens.weight"), m.store.v16("model.decoder.embed_positions.weight")
+            m.lm_head(self._ln(x, "model.decoder.layer_norm", b["y"]), out=b["logits"])
+        if select is not None:
+            select(self, b["logits"])
+
+    def spare_ok(self, Q):
+        return self.clamp_pos and Q <= F.MQ_MAX
+
+    def step(self, select=None, cur=None, head=True):
+        """One decoder step at position *t_dev for input ids `cur` (default: self.cur); then t_dev += 1.
+        select = (sup, beg, eos, done, ids, P) runs greedy selection into ids[:, t+1] and cur.  head=False stops
+        after the last layer (a step that only fills the caches)."""
+        m, B, d, H, T_max = self.m, self.B, self.d, self.H, self.T_max
+        cur = self.cur if cur is None else cur
+        E, Pe = self._embed_tables()
         x, o, t_dev = self.x, self.o, self.t_dev
         ks = self.k_start if self.padded else None
-        F.embed_step(self.cur, E, Pe, x, t_dev, T_max, pos_off=self.pos_off if self.shifted else None)
+        if self.clamp_pos:           # spare rows past the length cap: their positions clamp to the table
+            assert B == 1 and not self.shifted
+            F.embed_step_multi(cur, E, Pe, x, t_dev, 1)
+        else:
+            F.embed_step(cur, E, Pe, x, t_dev, T_max, pos_off=self.pos_off if self.shifted else None)
         sb = T_max * 2 * d
         for i in range(m.config.decoder_layers):
             p = f"model.decoder.layers.{i}"
@@ -217,10 +299,10 @@ class DecodeSession:
             self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), self.h,
                          flags=F.GEMM_ROUND | F.GEMM_GELU)
             self._lin(self.h, m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
-        if self.gemv_ln:
+        if head and self.gemv_ln:
             self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None,
                          self.logits)
-        else:
+        elif head:
             m.lm_head(self._ln(x, "model.decoder.layer_norm"), out=self.logits)
         if select is not None:
             select(self)
@@ -300,22 +382,29 @@ class _Select:
             raise ValueError("sampling needs a tracking selector (track=True)")
 
     def __call__(self, sess):
-        B = sess.B
+        self.launch(sess.logits, sess.t_dev, sess.cur, B=sess.B)
+
+    def launch(self, logits, t_dev, next_ids, col=1, sum_logp=None, B=1):
+        """The selection kernel this selector's mode takes (plain, timestamps, or the tracking forms with their
+        per-row control word) on `logits` ([B][Vp] rows) into ids[:, *t_dev + col] and next_ids.  sum_logp: where the
+        tracking forms accumulate (default: the selector's running sum)."""
+        Vp = logits.stride(0)
         if self.track:
+            slp = self.sum_logp if sum_logp is None else sum_logp
             if self.ts:
-                F.select_sample_ts(sess.logits, sess.m.Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids,
-                                   1, sess.cur, self.last_ts, self.P, self.ctl, self.sum_logp, ts_begin=self.no_ts + 1,
-                                   no_ts=self.no_ts, max_initial=self.max_initial, t_dev=sess.t_dev)
+                F.select_sample_ts(logits, Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids,
+                                   col, next_ids, self.last_ts, self.P, self.ctl, slp, ts_begin=self.no_ts + 1,
+                                   no_ts=self.no_ts, max_initial=self.max_initial, t_dev=t_dev)
             else:
-                F.select_sample(sess.logits, sess.m.Vp, B, self.V, self.sup, self.beg, False, self.eos, self.done,
-                                self.ids, 1, sess.cur, self.ctl, self.sum_logp, t_dev=sess.t_dev, begin_col=self.P)
+                F.select_sample(logits, Vp, B, self.V, self.sup, self.beg, False, self.eos, self.done,
+                                self.ids, col, next_ids, self.ctl, slp, t_dev=t_dev, begin_col=self.P)
         elif self.ts:
-            F.greedy_select_ts(sess.logits, sess.m.Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids, 1,
-                               sess.cur, self.last_ts, self.P, ts_begin=self.no_ts + 1, no_ts=self.no_ts,
-                               max_initial=self.max_initial, t_dev=sess.t_dev)
+            F.greedy_select_ts(logits, Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids, col,
+                               next_ids, self.last_ts, self.P, ts_begin=self.no_ts + 1, no_ts=self.no_ts,
+                               max_initial=self.max_initial, t_dev=t_dev)
         else:
-            F.greedy_select(sess.logits, sess.m.Vp, B, self.V, self.sup, self.beg, False, self.eos, self.done, self.ids,
-                            1, sess.cur, t_dev=sess.t_dev, begin_col=self.P)
+            F.greedy_select(logits, Vp, B, self.V, self.sup, self.beg, False, self.eos, self.done, self.ids,
+                            col, next_ids, t_dev=t_dev, begin_col=self.P)
 
 
 class _Decoder:
@@ -373,6 +462,132 @@ class _Decoder:
         B = gen.shape[0]
         first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full((B,), gen.shape[1]))
         L = int(min(gen.shape[1], int(first.max()) + 1)) if B else 0
+        return gen[:, :L]
+
+
+# Drafted tokens per round when generate(assistant_model=...) is given no num_assistant_tokens.  A guess from byte
+# counts, not a measurement: a large-v2 verify pass reads the decoder's weights once whatever Q is, a distil-32-2
+# draft step reads 1/16 of the layers plus the LM head, so a handful of drafts costs little beside one target step
+# (tools/bench_spec.py times both; the end-to-end gain depends on the acceptance rate of real checkpoints, which is
+# unmeasured).  HF's default (20 with a heuristic schedule) differs; for greedy decoding the output does not depend on it.
+DEFAULT_ASSISTANT_TOKENS = 4
+MAX_ASSISTANT_TOKENS = F.MQ_MAX - 1
+
+
+class _SpecDecoder:
+    """Assisted (speculative) greedy decode of ONE window: _Decoder.run's signature and result.  A round: the
+    assistant drafts k tokens with its own DecodeSession (k + 1 steps: the last one only puts the last draft's K/V
+    into the assistant's cache, without the LM head, so that a fully accepted round leaves the assistant caught up),
+    the target scores the k + 1 positions in one pass (DecodeSession.step_multi), k + 1 launches of the selection
+    kernel the plain decode would have used pick the target's token of each position -- launch j + 1 sees the right
+    context exactly when draft j was accepted -- and tw_spec_accept keeps the accepted prefix and rolls the rest
+    back, all on the device.  The round is position-independent, so it is captured once as one HIP graph; the host
+    reads the step counter and the finished flag every 4 rounds.
+    Both models write one id matrix: the drafts go to columns t+1 .. t+k, where the assistant's timestamp rules and
+    then the target's selection read them, and the target's tokens overwrite them in place.  Every accepted
+    position's logits are those of the plain decode (a row of the step's Linears does not depend on how many rows
+    run with it; tw_decode_attn_mq computes each query as the single-query kernel does), so the ids, the summed
+    log-prob and the no-speech probability equal the plain decode's."""
+
+    def __init__(self, model, assistant, gc, Tk, P, max_length, timestamps, use_graph, track=False, k=None):
+        self.m, self.a, self.P, self.T_max, self.use_graph = model, assistant, P, max_length, use_graph
+        self.k = DEFAULT_ASSISTANT_TOKENS if k is None else int(k)
+        assert 1 <= self.k <= MAX_ASSISTANT_TOKENS
+        Q = self.k + 1
+        dev = model.device
+        V = model.config.vocab_size
+        self.sel = _Select(gc, 1, V, max_length + Q, P, dev, timestamps, track)
+        self.sel_a = _Select(gc, 1, V, 1, P, dev, timestamps, False)     # the assistant: plain greedy, own flags
+        self.sel_a.ids = self.sel.ids
+        self.B, self.Tk = 1, Tk
+        self.ns_logp = torch.zeros(1, dtype=torch.float32, device=dev) if track else None
+        self.vin = torch.zeros(Q, dtype=torch.int64, device=dev)         # [current token, draft 0 .. draft k-1]
+        self.sink = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.slots = torch.zeros(Q, dtype=torch.float32, device=dev) if track else None
+        self.done_snap = torch.zeros(1, dtype=torch.uint8, device=dev)
+        self.hist = torch.zeros(1 + max(1, max_length - P), dtype=torch.int32, device=dev)
+        self.sess = self.sess_a = self.graph = None
+        self.accepted = []               # per round of the last run: the number of drafts accepted
+
+    def _verify_select(self, sess, logits):
+        for j in range(self.k + 1):
+            self.sel.launch(logits[j:j + 1], sess.t_dev, self.sink, col=1 + j,
+                            sum_logp=self.slots[j:j + 1] if self.slots is not None else None)
+
+    def _round(self):
+        k, sel, sel_a, sa, st, vin = self.k, self.sel, self.sel_a, self.sess_a, self.sess, self.vin
+        for i in range(k + 1):
+            if i < k:
+                sa.step(lambda s, i=i: sel_a.launch(s.logits, s.t_dev, vin[i + 1:i + 2]), cur=vin[i:i + 1])
+            else:
+                sa.step(cur=vin[i:i + 1], head=False)
+        st.step_multi(k + 1, vin, self._verify_select)
+        F.spec_accept(vin[1:], k, sel.ids[0], self.T_max, sel.eos, st.t_dev, vin[:1], sel.done, self.done_snap,
+                      t_dev_a=sa.t_dev, done_a=sel_a.done, last_ts=sel.last_ts if sel.ts else None,
+                      last_ts_a=sel_a.last_ts if sel.ts else None, begin_col=self.P, ts_begin=sel.no_ts + 1,
+                      slots=self.slots, sum_logp=sel.sum_logp if self.slots is not None else None, hist=self.hist)
+
+    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False,
+            enc_a=None):
+        """enc_a: the assistant's encoder rows for this window (its own encoder's output, or the target's cast to the
+        assistant's dtype for a decoder-only assistant)."""
+        if pads is not None and any(int(p) for p in pads):
+            raise NotImplementedError("tw generate: assisted decoding takes unpadded prompts")
+        if isinstance(temperature, (list, tuple)):
+            temperature = temperature[0]
+        if temperature:
+            raise NotImplementedError("tw generate: assisted decoding is greedy (temperature 0)")
+        sel, sel_a, P, Q = self.sel, self.sel_a, self.P, self.k + 1
+        enc_a = enc16 if enc_a is None else enc_a
+        if self.sess is None:
+            self.sess = DecodeSession(self.m, enc16, 1, self.Tk, self.T_max, spare=Q)
+            self.sess_a = DecodeSession(self.a, enc_a, 1, enc_a.shape[0], self.T_max, spare=Q)
+        else:
+            self.sess.set_encoder(enc16)
+            self.sess_a.set_encoder(enc_a)
+        st, sa = self.sess, self.sess_a
+        sel.reset(prompt, 0.0, seed if not isinstance(seed, (list, tuple)) else seed[0])
+        sel_a.done.zero_()
+        sel_a.last_ts.fill_(-1)
+        self.done_snap.zero_()
+        self.hist.zero_()
+        if self.slots is not None:
+            self.slots.zero_()
+        st.t_dev.zero_()
+        sa.t_dev.zero_()
+        V = self.m.config.vocab_size
+        for t in range(P - 1):                                   # prefill both caches with the prompt
+            st.cur.copy_(sel.ids[:, t])
+            st.step()
+            if no_speech is not None and t == no_speech[0]:
+                F.token_logprob(st.logits, self.m.Vp, 1, V, no_speech[1], self.ns_logp)
+            sa.cur.copy_(sel.ids[:, t])
+            sa.step()
+        self.vin[:1].copy_(sel.ids[0, P - 1:P])
+        if self.use_graph and self.graph is None:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._round()
+            self.graph = g
+        r, t = 0, P - 1
+        while r < self.T_max - P:                                # every live round accepts at least one token
+            if self.use_graph:
+                self.graph.replay()
+            else:
+                self._round()
+            if r == 0 and no_speech is not None and no_speech[0] == P - 1:
+                F.token_logprob(st.mq["logits"], self.m.Vp, 1, V, no_speech[1], self.ns_logp)
+            r += 1
+            if r % 4 == 0:
+                t = int(st.t_dev)
+                if t + 1 >= self.T_max or bool(sel.done.all()):
+                    break
+        t = int(st.t_dev)
+        h = self.hist.tolist()
+        self.accepted = h[1:1 + h[0]]
+        gen = sel.ids[:, P:t + 1]
+        is_eos = (gen[0] == sel.eos).cpu()
+        L = min(gen.shape[1], int(is_eos.int().argmax()) + 1) if bool(is_eos.any()) else gen.shape[1]
         return gen[:, :L]
 
 
@@ -620,13 +835,20 @@ GENERATE_KEYWORDS = frozenset({"temperature", "compression_ratio_threshold", "lo
 @torch.no_grad()
 def generate(model, input_features=None, max_length=None, num_beams=1, return_timestamps=False, language=None,
              task=None, decoder_input_ids=None, max_new_tokens=None, encoder_outputs=None, attention_mask=None,
-             use_graph=None, prompt_ids=None, prompt_condition_type=None, **kw):
+             use_graph=None, prompt_ids=None, prompt_condition_type=None, assistant_model=None,
+             num_assistant_tokens=None, **kw):
     """HF WhisperGenerationMixin.generate (transformers 5.15 generation_whisper.py), the calls the reference makes.
     prompt_ids (run_eval.py:656-657 --prompt_text): 1-D ids from get_prompt_ids (<|startofprev|> + text), placed in
     front of the task prompt of every decoded window (_prepare_decoder_input_ids; with the default
     prompt_condition_type "first-segment" and no conditioning on previous text, HF puts it in front of each window of a
     long-form input, not only the first); the begin indices of the suppress / timestamp processors and the length cap
-    count it; the returned ids do not contain it.  Any keyword that is not implemented raises TypeError."""
+    count it; the returned ids do not contain it.
+    assistant_model (run_eval.py:524-545 --assistant_model_name_or_path, passed at :653-654): assisted (speculative)
+    greedy decoding of a single input -- a tw WhisperForConditionalGeneration with its own encoder, or a
+    WhisperForCausalLM decoding over this model's encoder output (the distilled student with the shared frozen
+    encoder); it drafts num_assistant_tokens tokens a round (default DEFAULT_ASSISTANT_TOKENS, at most
+    MAX_ASSISTANT_TOKENS; HF's default and schedule differ) and this model verifies them in one pass (_SpecDecoder).
+    The ids are those of the same call without an assistant.  Any keyword that is not implemented raises TypeError."""
     from .config import GenerationConfig
     unknown = sorted(set(kw) - GENERATE_KEYWORDS)
     if unknown:
@@ -646,6 +868,11 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if not prompt_ids:
             prompt_ids = None
     nb = 1 if num_beams is None else int(num_beams)
+    assist = check_assistant(model, assistant_model, num_assistant_tokens, nb)
+    if assist is not None:
+        rows = input_features.shape[0] if input_features is not None and encoder_outputs is None else None
+        if rows is not None and rows != 1:
+            raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
     temperature = kw.get("temperature")
     fb = dict(temperature=temperature if temperature is not None else 0.0,
               compression_ratio_threshold=kw.get("compression_ratio_threshold"),
@@ -666,7 +893,7 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     if encoder_outputs is None and input_features is not None and (input_features.shape[-1] > window or seek_loop):
         return _longform(model, gc, input_features, attention_mask, language, task, max_length, max_new_tokens,
                          use_graph, window, kw.get("_trace"), fallback_batch=bool(kw.get("fallback_batch", True)),
-                         num_beams=nb, prompt_ids=prompt_ids, **fb)
+                         num_beams=nb, prompt_ids=prompt_ids, assist=assist, **fb)
     if kw.get("do_sample") or fb["temperature"] not in (0, 0.0) or fb["logprob_threshold"] is not None \
             or fb["compression_ratio_threshold"] is not None or fb["no_speech_threshold"] is not None:
         # the reference applies fallback / thresholds to long-form inputs only (run_eval.py:659-685)
@@ -692,6 +919,17 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     max_length = total_length(cfg, gc, P, max_length, max_new_tokens)
     if P >= max_length:
         return torch.empty(B, 0, dtype=torch.int64, device=model.device)
+    if assist is not None:
+        if B != 1:
+            raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
+        enc_a = assistant_encoder(assist[0], model, enc16, input_features)
+        dec = _SpecDecoder(model, assist[0], gc, Tk, P, max_length, bool(return_timestamps), use_graph, k=assist[1])
+        if kw.get("_keep") is not None:
+            kw["_keep"].append(dec)
+        out = dec.run(enc16, prompt.to(model.device), enc_a=enc_a)
+        if kw.get("_trace") is not None:
+            kw["_trace"].append(dict(accepted=list(dec.accepted), num_assistant_tokens=dec.k))
+        return out
     if nb > 1:
         if not bool((prompt == prompt[:1]).all()):
             raise NotImplementedError("tw generate: beam search takes one prompt for every clip")
@@ -700,6 +938,54 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     if kw.get("_keep") is not None:          # tests: the decoder (and its device caches) outlive the call
         kw["_keep"].append(dec)
     return dec.run(enc16, prompt.to(model.device))
+
+
+_ASSIST_GC_KEYS = ("eos_token_id", "pad_token_id", "decoder_start_token_id", "suppress_tokens", "begin_suppress_tokens",
+                   "no_timestamps_token_id", "max_initial_timestamp_index", "lang_to_id", "task_to_id")
+
+
+def check_assistant(model, assistant, num_assistant_tokens, num_beams):
+    """The argument checks of generate(assistant_model=...) -> None or (assistant, k).  ValueError: beam search with
+    an assistant (as HF), a vocabulary or generation config that differs from the target's (the drafts are compared
+    id by id and selected with the target's rules), a decoder-only assistant of another width."""
+    if assistant is None:
+        if num_assistant_tokens is not None:
+            raise ValueError("tw generate: num_assistant_tokens needs an assistant_model")
+        return None
+    if num_beams > 1:
+        raise ValueError("tw generate: assisted decoding is greedy (num_beams must be 1), as HF's is")
+    k = DEFAULT_ASSISTANT_TOKENS if num_assistant_tokens is None else int(num_assistant_tokens)
+    if k < 1:
+        raise ValueError(f"num_assistant_tokens={num_assistant_tokens!r}: at least 1")
+    k = min(k, MAX_ASSISTANT_TOKENS)
+    cfg, ac = model.config, getattr(assistant, "config", None)
+    if ac is None:
+        raise ValueError("tw generate: assistant_model must be a tw WhisperForConditionalGeneration or WhisperForCausalLM")
+    if ac.vocab_size != cfg.vocab_size:
+        raise ValueError(f"tw generate: the assistant's vocabulary ({ac.vocab_size}) differs from the target's "
+                         f"({cfg.vocab_size})")
+    ga, gt = assistant.generation_config, model.generation_config
+    if ga is not None and gt is not None:
+        for key in _ASSIST_GC_KEYS:
+            va, vt = (ga.get(key) if hasattr(ga, "get") else getattr(ga, key, None)), \
+                (gt.get(key) if hasattr(gt, "get") else getattr(gt, key, None))
+            if va is not None and vt is not None and va != vt:
+                raise ValueError(f"tw generate: the assistant's generation config differs from the target's in {key}")
+    if getattr(assistant, "decoder_only", False) and ac.d_model != cfg.d_model:
+        raise ValueError(f"tw generate: a decoder-only assistant decodes over the target's encoder output: d_model "
+                         f"{ac.d_model} != {cfg.d_model}")
+    return assistant, k
+
+
+def assistant_encoder(assistant, model, enc16, input_features):
+    """The assistant's encoder rows for one window: a decoder-only assistant (WhisperForCausalLM) takes the
+    target's, cast to its own activation dtype; any other runs its own encoder on the same features."""
+    if getattr(assistant, "decoder_only", False):
+        return enc16 if enc16.dtype == assistant.act_dtype else enc16.to(assistant.act_dtype)
+    if input_features is None:
+        raise ValueError("tw generate: an assistant with its own encoder needs input_features (encoder_outputs are "
+                         "the target's)")
+    return assistant.encode(assistant.conv_input(input_features))
 
 
 def batch_rows_independent(model):
@@ -780,7 +1066,7 @@ def conditioned_prompts(init, segments, cond_on, conditioned, prev_sot, cut_off,
 def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace, max_length, max_new_tokens,
                       compression_ratio_threshold, logprob_threshold, no_speech_threshold, fallback_batch, decoder, trim,
                       seeds_of, ns_token, ts_begin, eos, pad, enc_rows=32, n_task=None, cond=False, prev_sot=None,
-                      cut_off=None):
+                      cut_off=None, assist=None):
     """HF's batched sequential long-form (generation_whisper.py:785-898 with generate_with_fallback :970-1117): every
     recording of the call stays in ONE batch window after window -- each seek iteration cuts the current 30 s window
     of every unfinished recording at its own seek (_get_input_segment, zero-padded), encodes them together, decodes
@@ -808,7 +1094,9 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
     position ids for Whisper), so a padded row is HF's row, not the decode of its unpadded prompt.
     As in HF, the conditioned form starts once recording 0 has a segment, and from then on a row without previous
     text carries <|startofprev|> alone.  init: the unconditioned prompt (prompt_ids + task prompt); n_task: the
-    length of its task part (the <|startoftranscript|> position counts back from the end)."""
+    length of its task part (the <|startoftranscript|> position counts back from the end).
+    assist = (assistant, k) (one recording): the temperature-0 attempt of each window is assisted (_SpecDecoder: the
+    same tokens and gate values); sampled attempts use the plain decoder."""
     model_cfg = model.config
     dev = model.device
     nmel = feats.shape[1]
@@ -834,7 +1122,7 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
             raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
         ns = (P - n_task, ns_token) if no_speech_threshold is not None else None
         # encode the current windows together (chunks of enc_rows bound the encoder's activations)
-        enc = {}
+        enc, enc_as = {}, {}
         for c0 in range(0, len(active), enc_rows):
             rows = active[c0:c0 + enc_rows]
             segb = torch.zeros(len(rows), nmel, window, dtype=torch.float32, device=dev)
@@ -844,6 +1132,8 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
             tk = e.shape[0] // len(rows)
             for i, b in enumerate(rows):
                 enc[b] = e[i * tk:(i + 1) * tk]
+            if assist is not None:               # one recording: the assistant's rows for the same window
+                enc_as[rows[0]] = assistant_encoder(assist[0], model, enc[rows[0]], segb)
             del segb
         result = {}                       # b -> (accepted tokens, skip)
         pending = list(active)
@@ -859,14 +1149,16 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
             one = len({b for b, _ in rows_att}) == 1
             # the rows' encoder outputs: one window shared by every row (its K/V projected once), else gathered
             e16 = enc[rows_att[0][0]] if one else torch.cat([enc[b] for b, _ in rows_att])
-            d_ = decoder(P, ml, nb)
             tl = [temps[f] or 0.0 for _, f in rows_att]
+            assisted = assist is not None and nb == 1 and not tl[0]
+            d_ = decoder(P, ml, nb, spec=assisted)
             sl = [seeds[b][f] for b, f in rows_att]
             pads = [P - len(prompts[b]) for b, _ in rows_att]
             rows_p = [[pad] * n_ + prompts[b] for n_, (b, _) in zip(pads, rows_att)]
             raws = d_.run(e16, torch.tensor(rows_p, dtype=torch.int64, device=dev),
                           temperature=tl if nb > 1 else tl[0], seed=sl if nb > 1 else sl[0], no_speech=ns,
-                          **(dict(pads=pads) if cond else {})).tolist()
+                          **(dict(pads=pads) if cond else {}),
+                          **(dict(enc_a=enc_as[rows_att[0][0]]) if assisted else {})).tolist()
             del e16
             # a batch is cut at its LAST row's first eos: each row is cut at its own first eos, what its own decode
             # returns
@@ -891,12 +1183,14 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
                 elif trace is not None:
                     trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(prompts[b]), raw=list(raw),
                                       batch=nb))
+                if trace is not None and assisted:
+                    trace[-1]["accepted"] = list(d_.accepted)
                 result[b] = (raw, skip, temps[f])
                 if not needs:
                     decided.add(b)
             pending = [b for b in pending if b not in decided]
             level = levels[-1] + 1
-        del enc
+        del enc, enc_as
         for b in active:
             seq, skip, t_acc = result[b]
             n = nfr[b]
@@ -931,7 +1225,7 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
 def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
               trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
               no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
-              prompt_ids=None):
+              prompt_ids=None, assist=None):
     """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from
     `seek`; each window decoded with timestamp rules at the first temperature of `temperature` and
     re-decoded at the next one while HF's fallback test fails (compression ratio of the token bytes,
@@ -970,8 +1264,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
         prev_sot = sup[-2] if len(sup) >= 2 else None
     decoders = {}
 
-    def decoder(P, ml, nb=1):
-        key = (P, ml, nb)
+    def decoder(P, ml, nb=1, spec=False):
+        key = (P, ml, nb, spec)
         if key in decoders:
             decoders[key] = decoders.pop(key)            # most recently used last
         else:
@@ -979,7 +1273,11 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
             # large-v2): keep the three most recently used
             while len(decoders) >= 3:
                 decoders.pop(next(iter(decoders)))
-            decoders[key] = _Decoder(model, gc, nb, cfg.max_source_positions, P, ml, True, use_graph, track)
+            if spec:
+                decoders[key] = _SpecDecoder(model, assist[0], gc, cfg.max_source_positions, P, ml, True, use_graph,
+                                             track, k=assist[1])
+            else:
+                decoders[key] = _Decoder(model, gc, nb, cfg.max_source_positions, P, ml, True, use_graph, track)
         return decoders[key]
 
     def trim(raw):
@@ -1002,7 +1300,7 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
                                  max_new_tokens, compression_ratio_threshold, logprob_threshold, no_speech_threshold,
                                  fallback_batch, decoder, trim, seeds_of, ns_token, ts_begin, eos, pad,
                                  n_task=len(task_init), cond=bool(condition_on_prev_tokens), prev_sot=prev_sot,
-                                 cut_off=cut_off)
+                                 cut_off=cut_off, assist=assist)
     # beam search, and conditioning on the previous windows' text for a single recording: one recording at a time
     # (several conditioned recordings decode as one batch above, their prompts left-padded per row)
     seg_in = torch.zeros(1, nmel, window, dtype=torch.float32, device=dev)
@@ -1023,7 +1321,9 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
             ml = total_length(cfg, gc, P, max_length, max_new_tokens)
             if P >= ml:
                 raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
-            dec = decoder(P, ml)
+            assisted = assist is not None and nbeam == 1 and not temps[0]      # the temperature-0 attempt
+            dec = decoder(P, ml, spec=assisted)
+            enc_a = assistant_encoder(assist[0], model, enc16, seg_in) if assisted else None
             ptens = torch.tensor([prompt], dtype=torch.int64, device=dev)
             ns = (P - len(task_init), ns_token) if no_speech_threshold is not None else None
             skip, t_acc, seq = False, temps[0], []
@@ -1058,7 +1358,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
                         e_ = enc16                           # shared by the rows (DecodeSession.set_encoder)
                         p_ = ptens.repeat(nb, 1)
                     raws = d_.run(e_, p_, temperature=tl if len(tl) > 1 else tl[0],
-                                  seed=sl if len(sl) > 1 else sl[0], no_speech=ns).tolist()
+                                  seed=sl if len(sl) > 1 else sl[0], no_speech=ns,
+                                  **(dict(enc_a=enc_a) if d_ is dec and assisted else {})).tolist()
                     # a batch is cut at its LAST row's first eos, so a row that finished earlier carries extra eos
                     # (=pad) columns; each row is cut at its own first eos, which is what its batch-1 decode returns
                     raws = [row_tokens(r, eos) for r in raws]
@@ -1084,6 +1385,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
                     elif trace is not None:
                         trace.append(dict(b=b, seek=seek, n=n, T=temp, prompt=list(prompt), raw=list(raw),
                                           batch=nbatch))
+                    if trace is not None and d_ is dec and assisted:
+                        trace[-1]["accepted"] = list(dec.accepted)
                     seq, t_acc = raw, temp
                     if not needs:
                         done_here = True

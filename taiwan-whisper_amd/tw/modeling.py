@@ -768,6 +768,20 @@ class WhisperForConditionalGeneration:
         return generate(self, input_features, **kw)
 
 
+class WhisperForCausalLM(WhisperForConditionalGeneration):
+    """The decoder of a distilled student used as the assistant of assisted decoding over the TARGET's encoder output
+    (run_eval.py:524-545: AutoModelForCausalLM for an assistant that is not an openai/ checkpoint -- the student
+    trained with the teacher's frozen encoder).  The same loader and parameter layout as
+    WhisperForConditionalGeneration (a checkpoint without encoder tensors loads: from_state_dict is not strict; the
+    encoder segment then stays unused); `decoder_only` tells generate(assistant_model=...) to feed it the target's
+    encoder rows -- equal d_model required, cast when the dtypes differ -- instead of running an encoder of its own."""
+    decoder_only = True
+
+    def encode(self, conv_in, tape=None):
+        raise RuntimeError("tw: WhisperForCausalLM has no encoder of its own; it decodes over the target model's "
+                           "encoder output (generate(assistant_model=...))")
+
+
 # =============================================================================================
 # backward (student).  Walks a forward tape in reverse; every weight / bias gradient is
 # accumulated straight into the flat fp32 gradient buffer (model.grad) with autocast's rounding

@@ -507,6 +507,82 @@ def decode_attn(q, sqb, k, ldk, skb, v, ldv, svb, o, sob, B, H, Tk, scale, tk_de
     return o
 
 
+MQ_MAX = 8             # query rows per batch row of decode_attn_mq
+MQ_LDS = 12288         # score floats of its one-workgroup path (csrc/decode_impl.h DA_MQ_LDS)
+
+
+def decode_attn_mq(q, sqb, sqq, k, ldk, skb, v, ldv, svb, o, sob, soq, B, H, Q, Tk, scale, tk_dev=None, tk_max=None,
+                   hsk=None, hsv=None, k_start=None, causal=False, head_dim=64):
+    """decode_attn for Q consecutive query rows per batch row (tw_decode_attn_mq): query j of row b at
+    q + b*sqb + j*sqq attends keys [k_start[b], Tk (+ *tk_dev) (+ j when causal)); each K / V row is loaded once for
+    all Q queries.  tk_max bounds the rows the LAST query may read when Tk comes from the device."""
+    hd = int(head_dim)
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+        assert t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16, torch.float32), nm
+    if k_start is not None:
+        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
+        _need(k_start, B, "decode_mq k_start")
+    if tk_dev is not None:
+        assert tk_dev.dtype == torch.int32 and tk_max is not None
+    if 1 <= Q <= MQ_MAX and hd == 64 and B > 0 and H > 0:      # extents of a call the library will launch
+        rows = Tk + (Q - 1 if causal else 0) if tk_dev is None else tk_max
+        hk, hv = (hd if hsk is None else int(hsk)), (hd if hsv is None else int(hsv))
+        _need(q, (B - 1) * sqb + (Q - 1) * sqq + H * hd, "decode_mq q")
+        _need(k, (B - 1) * skb + (rows - 1) * ldk + (H - 1) * hk + hd, "decode_mq k")
+        _need(v, (B - 1) * svb + (rows - 1) * ldv + (H - 1) * hv + hd, "decode_mq v")
+        _need(o, (B - 1) * sob + (Q - 1) * soq + H * hd, "decode_mq o")
+    else:
+        hk = hv = hd
+        rows = 0
+    work = 2 * B * rows * H * hd * q.element_size()
+    fn = lambda: call("tw_decode_attn_mq", q.data_ptr(), sqb, sqq, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb,
+                      hv, o.data_ptr(), sob, soq, B, H, Q, Tk, _ptr(tk_dev), _ptr(k_start), int(bool(causal)), hd,
+                      float(scale), _dt(q), _stream())
+    KernelTimer.wrap("decode_attn_mq_self" if tk_dev is not None else "decode_attn_mq_cross", work, fn)
+    return o
+
+
+def embed_step_multi(ids, tok, pos, out, t_dev, Q):
+    """out[j] = tok[ids[j]] + pos[min(*t_dev + j, len(pos) - 1)] for j < Q (tw_embed_step_multi)."""
+    D = tok.shape[1]
+    assert ids.dtype == torch.int64 and t_dev.dtype == torch.int32 and ids.is_contiguous()
+    assert pos.shape[1] == D and pos.is_contiguous() and tok.is_contiguous()
+    _need(ids, Q, "embed_step_multi ids")
+    _need(out, Q * D, "embed_step_multi out")
+    call("tw_embed_step_multi", ids.data_ptr(), tok.data_ptr(), _dt(tok), pos.data_ptr(), _dt(pos), out.data_ptr(),
+         _dt(out), Q, D, t_dev.data_ptr(), pos.shape[0], _stream())
+    return out
+
+
+def spec_accept(drafts, k, ids_row, t_cap, eos, t_dev, cur, done, done_snap, *, t_dev_a=None, cur_a=None, done_a=None,
+                last_ts=None, last_ts_a=None, begin_col=0, ts_begin=0, slots=None, sum_logp=None, hist=None):
+    """tw_spec_accept on one row (include/tw_hip.h): ids_row is that row of the id matrix and holds at least
+    t_cap + k + 1 columns, so a round that starts at the last column t_cap - 1 stays inside it."""
+    assert drafts.dtype == torch.int64 and ids_row.dtype == torch.int64 and ids_row.dim() == 1
+    assert ids_row.stride(0) == 1 and cur.dtype == torch.int64 and 1 <= k < MQ_MAX
+    _need(drafts, k, "spec_accept drafts")
+    _need(ids_row, t_cap + k + 1, "spec_accept ids")
+    for t, dt, nm in ((t_dev, torch.int32, "t_dev"), (t_dev_a, torch.int32, "t_dev_a"), (cur, torch.int64, "cur"),
+                      (cur_a, torch.int64, "cur_a"), (done, torch.uint8, "done"), (done_a, torch.uint8, "done_a"),
+                      (done_snap, torch.uint8, "done_snap"), (last_ts, torch.int32, "last_ts"),
+                      (last_ts_a, torch.int32, "last_ts_a"), (sum_logp, torch.float32, "sum_logp")):
+        if t is not None:
+            assert t.dtype == dt, nm
+            _need(t, 1, f"spec_accept {nm}")
+    if slots is not None:
+        assert slots.dtype == torch.float32 and sum_logp is not None
+        _need(slots, k + 1, "spec_accept slots")
+    hist_cap = 0
+    if hist is not None:
+        assert hist.dtype == torch.int32 and hist.is_contiguous()
+        hist_cap = hist.numel()
+        _need(hist, hist_cap, "spec_accept hist")
+    call("tw_spec_accept", drafts.data_ptr(), int(k), ids_row.data_ptr(), int(t_cap), int(eos), t_dev.data_ptr(),
+         _ptr(t_dev_a), cur.data_ptr(), _ptr(cur_a), done.data_ptr(), _ptr(done_a), done_snap.data_ptr(),
+         _ptr(last_ts), _ptr(last_ts_a), int(begin_col), int(ts_begin), _ptr(slots), _ptr(sum_logp), _ptr(hist),
+         hist_cap, _stream())
+
+
 def token_bitmask(ids, V, device):
     """V-bit uint32 mask (as int32 storage) with the given token ids set."""
     words = torch.zeros((V + 31) // 32, dtype=torch.int64)
