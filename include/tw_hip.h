@@ -134,6 +134,11 @@ int tw_logmel(const float* wav, int B, const float* basis, const int* mel_start,
  * n_samples must exceed 200 (the reflect pad).  tw_logmel == tw_logmel_len(n_samples = 480000). */
 int tw_logmel_len(const float* wav, int B, int64_t n_samples, const float* basis, const int* mel_start,
                   const float* mel_w, float* mel_out, void* conv_in, void* workspace, tw_stream_t stream);
+/* The same front end with the mel count as an argument: n_mels = 80 (identical to tw_logmel_len) or 128
+ * (the large-v3 family's num_mel_bins); any other count is TW_EINVAL.  mel_start [n_mels], mel_w [n_mels][32]
+ * -> mel_out [B][n_mels][n_samples/160], conv_in [B][n_samples/160 + 2][n_mels] bf16. */
+int tw_logmel_mels(const float* wav, int B, int64_t n_samples, int n_mels, const float* basis, const int* mel_start,
+                   const float* mel_w, float* mel_out, void* conv_in, void* workspace, tw_stream_t stream);
 int tw_mel_to_conv_input(const float* mel, void* xt, int B, int nmel, int T, tw_stream_t stream);
 
 /* Decoder token + learned position embedding (HF modeling_whisper.py:736,754-761) and its

@@ -65,7 +65,9 @@ def _dims(d, enc, dec, heads, ffn):
 
 
 # architecture dims of the checkpoints the reference names (openai/whisper-* config.json; distil-32-2 is
-# create_student_model.py with --decoder_layers 2 from large-v2)
+# create_student_model.py with --decoder_layers 2 from large-v2).  The large-v3 family (large-v3, its 4-decoder-layer
+# turbo pruning and the 32-2 distil-large-v3) has 128 mel bins and one more language token (<|yue|>): V = 51866.
+_V3 = dict(num_mel_bins=128, vocab_size=51866)
 MODEL_DIMS = {
     "tiny": _dims(384, 4, 4, 6, 1536),
     "base": _dims(512, 6, 6, 8, 2048),
@@ -73,6 +75,9 @@ MODEL_DIMS = {
     "medium": _dims(1024, 24, 24, 16, 4096),
     "large-v2": _dims(1280, 32, 32, 20, 5120),
     "distil-32-2": _dims(1280, 32, 2, 20, 5120),
+    "large-v3": dict(_dims(1280, 32, 32, 20, 5120), **_V3),
+    "large-v3-turbo": dict(_dims(1280, 32, 4, 20, 5120), **_V3),
+    "distil-large-v3": dict(_dims(1280, 32, 2, 20, 5120), **_V3),
 }
 
 # openai/whisper-large-v2 generation_config.json suppress_tokens (the multilingual checkpoints' list)
@@ -83,12 +88,26 @@ LARGE_V2_SUPPRESS = [1, 2, 7, 8, 9, 10, 14, 25, 26, 27, 28, 29, 31, 58, 59, 60, 
                      18956, 20075, 21675, 22520, 26130, 26161, 26435, 28279, 29464, 31650, 32302, 32470,
                      36865, 42863, 47425, 49870, 50254, 50258, 50358, 50359, 50360, 50361, 50362]
 
+# The large-v3 family's list, derived from the one above rather than copied from a file: <|yue|> takes id 50358, so
+# every suppressed id >= 50358 is one higher (<|translate|> ... <|nospeech|> = 50359 ... 50363); the rest is unchanged.
+LARGE_V3_SUPPRESS = [t + 1 if t >= 50358 else t for t in LARGE_V2_SUPPRESS]
+
 
 GEN_DEFAULTS = dict(
     decoder_start_token_id=50258, eos_token_id=50257, pad_token_id=50257, bos_token_id=50257,
     no_timestamps_token_id=50363, max_length=448, num_beams=1, suppress_tokens=[], begin_suppress_tokens=[220, 50257],
     is_multilingual=True, lang_to_id={}, task_to_id={"transcribe": 50359, "translate": 50358},
 )
+
+
+def large_v3_generation_config(**extra) -> dict:
+    """The fields of a large-v3 family generation_config.json this engine reads, with that vocabulary's ids
+    (tw.data.SpecialTokens.for_vocab(51866)); for model directories written without one."""
+    gc = dict(GEN_DEFAULTS, no_timestamps_token_id=50364, suppress_tokens=list(LARGE_V3_SUPPRESS),
+              task_to_id={"transcribe": 50360, "translate": 50359},
+              lang_to_id={"<|en|>": 50259, "<|zh|>": 50260, "<|yue|>": 50358})
+    gc.update(extra)
+    return gc
 
 
 class GenerationConfig(dict):

@@ -12,6 +12,7 @@
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 
 import numpy as np
@@ -23,8 +24,70 @@ TIMESTAMP_BEGIN = NOTIMESTAMPS   # tokenizer.all_special_ids[-1] (:1129)
 WHITESPACE = 220
 
 
+@dataclasses.dataclass(frozen=True)
+class SpecialTokens:
+    """Where a Whisper vocabulary puts its special tokens.  The multilingual vocabularies differ in the language
+    count only: 51865 (up to large-v2) has 99 languages, 51866 (the large-v3 family) adds <|yue|> after <|su|>, so
+    every id from <|translate|> upward is one higher.  `timestamp_begin` is the label side's threshold, the
+    reference's `tokenizer.all_special_ids[-1]` (run_distillation.py:1129) = <|notimestamps|>: ids above it are
+    timestamps; <|0.00|> is `first_timestamp`."""
+    eot: int
+    sot: int
+    translate: int
+    transcribe: int
+    startoflm: int
+    startofprev: int
+    nospeech: int
+    notimestamps: int
+    timestamp_begin: int
+    n_languages: int
+
+    @property
+    def pad(self):
+        return self.eot
+
+    @property
+    def first_timestamp(self):
+        return self.notimestamps + 1
+
+    @classmethod
+    def _after_languages(cls, n_languages):
+        t = SOT + 1 + n_languages            # <|translate|> follows the language tokens
+        return cls(eot=EOT, sot=SOT, translate=t, transcribe=t + 1, startoflm=t + 2, startofprev=t + 3,
+                   nospeech=t + 4, notimestamps=t + 5, timestamp_begin=t + 5, n_languages=n_languages)
+
+    @classmethod
+    def for_vocab(cls, vocab_size):
+        if vocab_size == 51865:
+            return cls._after_languages(99)
+        if vocab_size == 51866:
+            return cls._after_languages(100)
+        raise ValueError(f"no special-token layout known for vocab_size {vocab_size} (51865: up to large-v2, "
+                         "51866: the large-v3 family)")
+
+    @classmethod
+    def from_tokenizer(cls, tok):
+        """From a tokenizer's own table (`convert_tokens_to_ids`, as the reference's collator and :1129 do)."""
+        ids = {n: int(tok.convert_tokens_to_ids(f"<|{n}|>")) for n in
+               ("endoftext", "startoftranscript", "translate", "transcribe", "startoflm", "startofprev",
+                "notimestamps")}
+        nospeech = tok.convert_tokens_to_ids("<|nospeech|>")
+        if nospeech is None or int(nospeech) != ids["notimestamps"] - 1:    # older tokenizer files: <|nocaptions|>
+            nospeech = ids["notimestamps"] - 1
+        return cls(eot=ids["endoftext"], sot=ids["startoftranscript"], translate=ids["translate"],
+                   transcribe=ids["transcribe"], startoflm=ids["startoflm"], startofprev=ids["startofprev"],
+                   nospeech=int(nospeech), notimestamps=ids["notimestamps"], timestamp_begin=ids["notimestamps"],
+                   n_languages=ids["translate"] - ids["startoftranscript"] - 1)
+
+
+LARGE_V2_TOKENS = SpecialTokens.for_vocab(51865)
+
+
 def prepare_labels(token_ids_batch, prev_batch, rng, timestamp_probability=0.5, condition_on_prev_probability=0.2,
-                   max_label_length=448, is_multilingual=True, has_prev_column=True):
+                   max_label_length=448, is_multilingual=True, has_prev_column=True, specials=None):
+    """`specials`: the vocabulary's SpecialTokens (default: the large-v2 layout of the module constants)."""
+    TIMESTAMP_BEGIN, STARTOFPREV = ((specials.timestamp_begin, specials.startofprev) if specials is not None else
+                                    (LARGE_V2_TOKENS.timestamp_begin, LARGE_V2_TOKENS.startofprev))
     timestamp_position = 3 if is_multilingual else 1
     cutoff = max_label_length // 2
     out, unprompted = [], []
@@ -61,7 +124,11 @@ def prepare_labels(token_ids_batch, prev_batch, rng, timestamp_probability=0.5, 
 
 class DataCollatorSpeechSeq2SeqWithPadding:
     def __init__(self, processor=None, decoder_start_token_id=SOT, decoder_prev_token_id=STARTOFPREV,
-                 input_padding="longest", target_padding="max_length", max_target_length=448, pad_token_id=PAD):
+                 input_padding="longest", target_padding="max_length", max_target_length=448, pad_token_id=PAD,
+                 specials=None):
+        if specials is not None:        # the vocabulary's layout decides the three ids
+            decoder_start_token_id, decoder_prev_token_id = specials.sot, specials.startofprev
+            pad_token_id = specials.pad
         self.processor = processor
         self.decoder_start_token_id = decoder_start_token_id
         self.decoder_prev_token_id = decoder_prev_token_id
@@ -92,7 +159,9 @@ class DataCollatorSpeechSeq2SeqWithPadding:
         return batch
 
 
-def synthetic_label_lists(B, seed=0, prompt_fraction=0.2, min_len=32, max_len=440, lang=ZH):
+def synthetic_label_lists(B, seed=0, prompt_fraction=0.2, min_len=32, max_len=440, lang=ZH, specials=None):
+    sp = LARGE_V2_TOKENS if specials is None else specials
+    EOT, SOT, TRANSCRIBE, NOTIMESTAMPS, STARTOFPREV = sp.eot, sp.sot, sp.transcribe, sp.notimestamps, sp.startofprev
     rng = np.random.Generator(np.random.PCG64(seed))
     out = []
     for _ in range(B):

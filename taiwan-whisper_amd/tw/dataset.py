@@ -40,8 +40,8 @@ from typing import Callable, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from .data import (EOT, NOTIMESTAMPS, SOT, STARTOFPREV, TRANSCRIBE, DataCollatorSpeechSeq2SeqWithPadding,
-                   prepare_labels)
+from .data import (EOT, LARGE_V2_TOKENS, NOTIMESTAMPS, SOT, STARTOFPREV, TRANSCRIBE,
+                   DataCollatorSpeechSeq2SeqWithPadding, SpecialTokens, prepare_labels)
 
 SAMPLING_RATE = 16000
 _TS_RE = re.compile(r"<\|\d{1,2}\.\d{2}\|>")
@@ -191,20 +191,25 @@ def whisper_special_tokens(n_languages: int = 99) -> dict:
     """Multilingual Whisper special-token ids (Appendix A of SURVEY.md; HF vocab order):
     <|endoftext|> 50257, <|startoftranscript|> 50258, language tokens from 50259 (<|en|>, <|zh|>, ...),
     <|translate|> 50358, <|transcribe|> 50359, <|startoflm|> 50360, <|startofprev|> 50361,
-    <|nocaptions|> 50362, <|notimestamps|> 50363, <|0.00|> ... <|30.00|> 50364 ... 51864."""
+    <|nocaptions|> 50362, <|notimestamps|> 50363, <|0.00|> ... <|30.00|> 50364 ... 51864.
+    n_languages=100 is the large-v3 table: <|yue|> 50358 follows <|su|>, every id from <|translate|> upward is one
+    higher (<|0.00|> ... <|30.00|> 50365 ... 51865) and 50363 is spelled <|nospeech|>."""
     langs = ["en", "zh", "de", "es", "ru", "ko", "fr", "ja", "pt", "tr", "pl", "ca", "nl", "ar", "sv", "it", "id",
              "hi", "fi", "vi", "he", "uk", "el", "ms", "cs", "ro", "da", "hu", "ta", "no", "th", "ur", "hr", "bg",
              "lt", "la", "mi", "ml", "cy", "sk", "te", "fa", "lv", "bn", "sr", "az", "sl", "kn", "et", "mk", "br",
              "eu", "is", "hy", "ne", "mn", "bs", "kk", "sq", "sw", "gl", "mr", "pa", "si", "km", "sn", "yo", "so",
              "af", "oc", "ka", "be", "tg", "sd", "gu", "am", "yi", "lo", "uz", "fo", "ht", "ps", "tk", "nn", "mt",
-             "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su"][:n_languages]
-    tab = {"<|endoftext|>": EOT, "<|startoftranscript|>": SOT}
+             "sa", "lb", "my", "bo", "tl", "mg", "as", "tt", "haw", "ln", "ha", "ba", "jw", "su", "yue"][:n_languages]
+    sp = LARGE_V2_TOKENS if n_languages <= 99 else SpecialTokens.for_vocab(51866)
+    tab = {"<|endoftext|>": sp.eot, "<|startoftranscript|>": sp.sot}
     for i, l in enumerate(langs):
         tab[f"<|{l}|>"] = 50259 + i
-    tab.update({"<|translate|>": 50358, "<|transcribe|>": TRANSCRIBE, "<|startoflm|>": 50360,
-                "<|startofprev|>": STARTOFPREV, "<|nocaptions|>": 50362, "<|notimestamps|>": NOTIMESTAMPS})
+    tab.update({"<|translate|>": sp.translate, "<|transcribe|>": sp.transcribe, "<|startoflm|>": sp.startoflm,
+                "<|startofprev|>": sp.startofprev,
+                ("<|nocaptions|>" if n_languages <= 99 else "<|nospeech|>"): sp.nospeech,
+                "<|notimestamps|>": sp.notimestamps})
     for i in range(1501):
-        tab["<|%.2f|>" % (i * 0.02)] = NOTIMESTAMPS + 1 + i
+        tab["<|%.2f|>" % (i * 0.02)] = sp.notimestamps + 1 + i
     return tab
 
 
@@ -214,16 +219,22 @@ class WhisperTokenizerAdapter:
     text between them goes to `text_encoder` (the BPE: an HF tokenizer's encode without special
     tokens when its files exist, any str -> ids callable otherwise); add_special_tokens=True wraps
     the ids in the prefix tokens [SOT, <|lang|>, <|task|>] (+ <|notimestamps|> unless
-    predict_timestamps) and <|endoftext|>.  Unknown <|...|> strings (e.g. <|continued|>) are text."""
+    predict_timestamps) and <|endoftext|>.  Unknown <|...|> strings (e.g. <|continued|>) are text.
+    `vocab_size` (51865 / 51866) or `specials` (a tw.data.SpecialTokens) picks the special-token layout; the
+    default is large-v2's."""
 
     def __init__(self, text_encoder: Callable[[str], List[int]], language: Optional[str] = "zh",
                  task: Optional[str] = "transcribe", predict_timestamps: bool = True,
-                 text_decoder: Optional[Callable[[List[int]], str]] = None):
-        self.special = whisper_special_tokens()
+                 text_decoder: Optional[Callable[[List[int]], str]] = None, vocab_size: Optional[int] = None,
+                 specials: Optional[SpecialTokens] = None):
+        if specials is None:
+            specials = LARGE_V2_TOKENS if vocab_size is None else SpecialTokens.for_vocab(vocab_size)
+        self.specials = specials
+        self.special = whisper_special_tokens(specials.n_languages)
         self.id_to_special = {v: k for k, v in self.special.items()}
         self.text_encoder, self.text_decoder = text_encoder, text_decoder
         self.set_prefix_tokens(language, task, predict_timestamps)
-        self.pad_token_id = self.eos_token_id = EOT
+        self.pad_token_id = self.eos_token_id = specials.eot
 
     def set_prefix_tokens(self, language=None, task=None, predict_timestamps=None):
         if language is not None:
@@ -232,17 +243,17 @@ class WhisperTokenizerAdapter:
             self.task = task
         if predict_timestamps is not None:
             self.predict_timestamps = predict_timestamps
-        p = [SOT]
+        p = [self.specials.sot]
         if getattr(self, "language", None):
             p.append(self.special[f"<|{self.language}|>"])
         if getattr(self, "task", None):
             p.append(self.special[f"<|{self.task}|>"])
         if not self.predict_timestamps:
-            p.append(NOTIMESTAMPS)
+            p.append(self.specials.notimestamps)
         self.prefix_tokens = p
 
     def timestamp_ids(self):
-        return list(range(NOTIMESTAMPS + 1, NOTIMESTAMPS + 1 + 1501))
+        return list(range(self.specials.first_timestamp, self.specials.first_timestamp + 1501))
 
     def encode(self, text: str, add_special_tokens: bool = True) -> List[int]:
         ids: List[int] = []
@@ -258,7 +269,7 @@ class WhisperTokenizerAdapter:
         if pos < len(text):
             ids.extend(self.text_encoder(text[pos:]))
         if add_special_tokens:
-            ids = self.prefix_tokens + ids + [EOT]
+            ids = self.prefix_tokens + ids + [self.specials.eot]
         return ids
 
     def __call__(self, text, add_special_tokens: bool = True):
@@ -271,7 +282,7 @@ class WhisperTokenizerAdapter:
     def decode(self, ids, skip_special_tokens: bool = True) -> str:
         out, run = [], []
         for t in (int(x) for x in ids):
-            if t in self.id_to_special or t > NOTIMESTAMPS:
+            if t in self.id_to_special or t > self.specials.notimestamps:
                 if run:
                     out.append(self.text_decoder(run) if self.text_decoder else "")
                     run = []
@@ -315,11 +326,13 @@ def shard_micro_batches(n_items: int, batch_size: int, rank: int, world: int, or
 def prepare_train_batch(features: Sequence[dict], tokenizer, rng: np.random.Generator, *,
                         text_column: str = "whisper_transcript", timestamp_probability: float = 0.5,
                         condition_on_prev_probability: float = 0.2, max_label_length: int = 448,
-                        is_multilingual: bool = True, collator: Optional[DataCollatorSpeechSeq2SeqWithPadding] = None):
+                        is_multilingual: bool = True, collator: Optional[DataCollatorSpeechSeq2SeqWithPadding] = None,
+                        specials: Optional[SpecialTokens] = None):
     """Host side of prepare_train_dataset (:1207-1274) + collator for one micro-batch: token ids of
     the transcripts / prompts, label sampling (tw.data.prepare_labels), padding.  Returns
-    (list of float32 waveforms, decoder_input_ids int64 [B, L-1], labels int64 [B, L-1])."""
-    collator = collator or DataCollatorSpeechSeq2SeqWithPadding(max_target_length=max_label_length)
+    (list of float32 waveforms, decoder_input_ids int64 [B, L-1], labels int64 [B, L-1]).  `specials`: the
+    vocabulary's special-token layout (default large-v2's)."""
+    collator = collator or DataCollatorSpeechSeq2SeqWithPadding(max_target_length=max_label_length, specials=specials)
     tok_batch, prev_batch = [], []
     for f in features:
         s = f[text_column]
@@ -328,7 +341,7 @@ def prepare_train_batch(features: Sequence[dict], tokenizer, rng: np.random.Gene
         prev_batch.append(tokenizer(p, add_special_tokens=False).input_ids if isinstance(p, str) else p)
     has_prev = any("condition_on_prev" in f for f in features)
     labels = prepare_labels(tok_batch, prev_batch, rng, timestamp_probability, condition_on_prev_probability,
-                            max_label_length, is_multilingual, has_prev_column=has_prev)
+                            max_label_length, is_multilingual, has_prev_column=has_prev, specials=specials)
     dec, lab = collator.collate_labels(labels)
     wavs = [np.asarray(f["audio"]["array"], dtype=np.float32) for f in features]
     return wavs, dec, lab
@@ -338,11 +351,13 @@ class DataFeed:
     """Per-rank prefetching feed: host preparation of the next `depth` micro-batches runs in a thread
     pool while the current step runs; `next()` copies the waveforms into pinned memory, ships them
     with one async H2D copy and runs tw_logmel on the GPU, returning the trainer's batch dict
-    (conv_input bf16 [B, 3002, 80] for the conv stem, decoder_input_ids, labels on the device)."""
+    (conv_input bf16 [B, 3002, 80] for the conv stem, decoder_input_ids, labels on the device).
+    `feature_extractor` (default: the 80-bin one) decides the mel count, e.g. the 128-bin front end of a large-v3
+    model directory (WhisperFeatureExtractor.from_pretrained); `specials=` among prep_kw its label layout."""
 
     def __init__(self, dataset, tokenizer, batch_size: int, *, rank: int = 0, world: int = 1, device=None,
                  seed: int = 42, epoch: int = 0, shuffle: bool = True, depth: int = 2, workers: int = 4,
-                 skip_batches: int = 0, **prep_kw):
+                 skip_batches: int = 0, feature_extractor=None, **prep_kw):
         from .feature_extraction import WhisperFeatureExtractor
         self.ds, self.tok, self.B = dataset, tokenizer, batch_size
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -353,7 +368,7 @@ class DataFeed:
         self.batches, self.n_real = batches[skip_batches:], real[skip_batches:]
         self.rng = np.random.Generator(np.random.PCG64([seed, epoch, rank]))
         self.prep_kw = prep_kw
-        self.fe = WhisperFeatureExtractor(device=self.device)
+        self.fe = feature_extractor if feature_extractor is not None else WhisperFeatureExtractor(device=self.device)
         self.pool = cf.ThreadPoolExecutor(max_workers=workers)
         self.depth = depth
         self._futs: list = []

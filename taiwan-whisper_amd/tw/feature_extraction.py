@@ -43,7 +43,7 @@ def mel_filters(n_freqs=201, n_mels=N_MELS, fmin=0.0, fmax=8000.0, sr=SAMPLING_R
 
 
 @functools.lru_cache(maxsize=None)
-def _host_tables():
+def _host_tables(n_mels=N_MELS):
     n = np.arange(N_FFT, dtype=np.float64)
     win = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / N_FFT)             # periodic Hann
     k = np.arange(201, dtype=np.float64)
@@ -51,10 +51,10 @@ def _host_tables():
     basis = np.zeros((N_FFT, 416), dtype=np.float64)
     basis[:, :201] = win[:, None] * np.cos(ang)
     basis[:, 208:208 + 201] = -win[:, None] * np.sin(ang)
-    fb = mel_filters()                                             # [201, 80]
-    start = np.zeros(N_MELS, dtype=np.int32)
-    w = np.zeros((N_MELS, MELW), dtype=np.float32)
-    for m in range(N_MELS):
+    fb = mel_filters(n_mels=n_mels)                                # [201, n_mels]
+    start = np.zeros(n_mels, dtype=np.int32)
+    w = np.zeros((n_mels, MELW), dtype=np.float32)
+    for m in range(n_mels):
         nz = np.nonzero(fb[:, m])[0]
         if nz.size == 0:
             continue
@@ -66,22 +66,25 @@ def _host_tables():
     return basis.astype(np.float32), start, w
 
 
-def mel_tables(device="cpu"):
-    b, s, w = _host_tables()
+def mel_tables(device="cpu", n_mels=N_MELS):
+    """(basis [400, 416], start [n_mels] int32, taps [n_mels, 32]) for the log-mel kernel; n_mels is 80, or 128 for
+    the large-v3 family."""
+    b, s, w = _host_tables(int(n_mels))
     return torch.from_numpy(b).to(device), torch.from_numpy(s).to(device), torch.from_numpy(w).to(device)
 
 
 class WhisperFeatureExtractor:
     """Drop-in for the two calls the reference makes.  `__call__` returns an object with
-    `.input_features` ([B, 80, 3000] fp32 on `device`); the time-major bf16 conv1 input is
-    also produced (`.conv_input`) so the encoder can skip a transpose."""
+    `.input_features` ([B, feature_size, 3000] fp32 on `device`; feature_size 80, or 128 for the
+    large-v3 family); the time-major bf16 conv1 input is also produced (`.conv_input`) so the
+    encoder can skip a transpose."""
 
     model_input_names = ["input_features"]
 
     def __init__(self, feature_size=80, sampling_rate=SAMPLING_RATE, hop_length=HOP, chunk_length=30, n_fft=N_FFT,
                  padding_value=0.0, device="cuda"):
-        if (feature_size, sampling_rate, hop_length, chunk_length, n_fft) != (80, 16000, 160, 30, 400):
-            raise NotImplementedError("tw log-mel kernel is specialised for Whisper's 80x3000 front end")
+        if feature_size not in (80, 128) or (sampling_rate, hop_length, chunk_length, n_fft) != (16000, 160, 30, 400):
+            raise NotImplementedError("tw log-mel kernel is specialised for Whisper's 80x3000 and 128x3000 front ends")
         self.feature_size, self.sampling_rate, self.padding_value = feature_size, sampling_rate, padding_value
         self.n_samples, self.nb_max_frames = N_SAMPLES, N_FRAMES
         self.device = device
@@ -89,12 +92,26 @@ class WhisperFeatureExtractor:
 
     def _tabs(self):
         if self._tables is None:
-            self._tables = mel_tables(self.device)
+            self._tables = mel_tables(self.device, self.feature_size)
         return self._tables
 
     @property
     def mel_filters(self):
-        return mel_filters().astype(np.float32)
+        return mel_filters(n_mels=self.feature_size).astype(np.float32)
+
+    @classmethod
+    def from_pretrained(cls, model_dir, device="cuda", **kw):
+        """The front end a checkpoint directory asks for: `feature_size` of its preprocessor_config.json, else
+        `num_mel_bins` of its config.json (a directory with neither is the 80-bin default)."""
+        import json
+        import os
+        size = None
+        for name, key in (("preprocessor_config.json", "feature_size"), ("config.json", "num_mel_bins")):
+            path = os.path.join(str(model_dir), name)
+            if size is None and os.path.exists(path):
+                with open(path) as f:
+                    size = json.load(f).get(key)
+        return cls(feature_size=N_MELS if size is None else int(size), device=device, **kw)
 
     @staticmethod
     def _as_list(raw_speech):
@@ -113,14 +130,14 @@ class WhisperFeatureExtractor:
         return out
 
     def extract(self, wav: torch.Tensor, want_conv_input: bool = True):
-        """wav: [B, n] fp32 (host or device) -> (mel [B,80,n//160] fp32, conv_in [B,n//160+2,80] bf16);
+        """wav: [B, n] fp32 (host or device) -> (mel [B,F,n//160] fp32, conv_in [B,n//160+2,F] bf16), F = feature_size;
         n = 480 000 for 30 s clips, any n > 200 for long-form inputs."""
         wav = wav.to(self.device, torch.float32).contiguous()
         B, n = wav.shape
         nfr = n // HOP
         basis, start, w = self._tabs()
-        mel = torch.empty(B, N_MELS, nfr, dtype=torch.float32, device=self.device)
-        conv = torch.empty(B, nfr + 2, N_MELS, dtype=torch.bfloat16, device=self.device) if want_conv_input else None
+        mel = torch.empty(B, self.feature_size, nfr, dtype=torch.float32, device=self.device)
+        conv = torch.empty(B, nfr + 2, self.feature_size, dtype=torch.bfloat16, device=self.device) if want_conv_input else None
         ops.logmel(wav, basis, start, w, mel, conv)
         return mel, conv
 

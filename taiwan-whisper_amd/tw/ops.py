@@ -280,16 +280,23 @@ def kl_ce(s_logits, t_logits, labels, V, n_valid, T=2.0, ce_w=0.8, kl_w=1.0, gra
 
 def logmel(wav, basis, mel_start, mel_w, mel_out, conv_in=None, workspace=None):
     """wav [B, n] fp32 -> mel_out [B, 80, n // 160] (+ conv_in [B, n // 160 + 2, 80] bf16).  n = 480 000 is the
-    30 s path (tw_logmel); any other n > 200 is the long-form path (tw_logmel_len)."""
+    30 s path (tw_logmel); any other n > 200 is the long-form path (tw_logmel_len).  The mel count is
+    mel_out.shape[1]: 80, or 128 (large-v3; tw_logmel_mels) with mel_start [128] and mel_w [128, 32]."""
     B, n = wav.shape
     nfr = n // 160
+    nmel = mel_out.shape[1]
     assert wav.dtype == torch.float32 and wav.is_contiguous() and n > 200
-    assert mel_out.shape == (B, 80, nfr) and mel_out.dtype == torch.float32 and mel_out.is_contiguous()
+    assert nmel in (80, 128), f"logmel: {nmel} mel bins (the kernel is built for 80 and 128)"
+    assert mel_out.shape == (B, nmel, nfr) and mel_out.dtype == torch.float32 and mel_out.is_contiguous()
+    assert mel_start.numel() == nmel and mel_w.shape == (nmel, 32), "logmel: tables are for another mel count"
     if conv_in is not None:
-        assert conv_in.shape == (B, nfr + 2, 80) and conv_in.dtype == torch.bfloat16 and conv_in.is_contiguous()
+        assert conv_in.shape == (B, nfr + 2, nmel) and conv_in.dtype == torch.bfloat16 and conv_in.is_contiguous()
     if workspace is None:
         workspace = torch.empty(B, dtype=torch.int32, device=wav.device)
-    if n == 480000:
+    if nmel != 80:
+        call("tw_logmel_mels", wav.data_ptr(), B, n, nmel, basis.data_ptr(), mel_start.data_ptr(), mel_w.data_ptr(),
+             mel_out.data_ptr(), _ptr(conv_in), workspace.data_ptr(), _stream())
+    elif n == 480000:
         call("tw_logmel", wav.data_ptr(), B, basis.data_ptr(), mel_start.data_ptr(), mel_w.data_ptr(),
              mel_out.data_ptr(), _ptr(conv_in), workspace.data_ptr(), _stream())
     else:

@@ -99,8 +99,11 @@ class ChunkTranscriber:
 
     def __init__(self, model, language: str = "zh", max_new_tokens: Optional[int] = None, device=None):
         from .feature_extraction import WhisperFeatureExtractor
+        from .data import SpecialTokens
         self.m = model
-        self.fe = WhisperFeatureExtractor(device=device or model.device)
+        # the front end and <|endoftext|> follow the model: 80 bins / 51865 ids up to large-v2, 128 / 51866 for large-v3
+        self.fe = WhisperFeatureExtractor(feature_size=model.config.num_mel_bins, device=device or model.device)
+        self.eot = SpecialTokens.for_vocab(model.config.vocab_size).eot
         self.language, self.max_new_tokens = language, max_new_tokens
 
     def __call__(self, chunks: Sequence[np.ndarray]) -> List[List[int]]:
@@ -111,7 +114,7 @@ class ChunkTranscriber:
         ids = self.m.generate(mel, language=self.language, task="transcribe", max_new_tokens=self.max_new_tokens)
         out = []
         for row in ids.tolist():
-            k = row.index(EOT) if EOT in row else len(row)
+            k = row.index(self.eot) if self.eot in row else len(row)
             out.append(row[:k])
         return out
 

@@ -99,7 +99,9 @@ def build_parser():
 
 def load_tokenizer(args):
     """The reference's WhisperTokenizerFast (+1501 timestamp tokens) when its files exist in the model
-    directory; else the special-token adapter over a byte-level text encoder (tests only)."""
+    directory; else the special-token adapter over a byte-level text encoder (tests only), with the special-token
+    layout of the student's config.json vocab_size (51865: up to large-v2, 51866: the large-v3 family)."""
+    from .config import WhisperConfig
     from .dataset import WhisperTokenizerAdapter
     path = args.tokenizer_name or args.model_name_or_path
     if not args.byte_level_text_tokenizer:
@@ -112,7 +114,19 @@ def load_tokenizer(args):
         return tok
     return WhisperTokenizerAdapter(lambda s: list(s.encode("utf-8")), language=args.language, task=args.task,
                                    predict_timestamps=args.timestamp_probability > 0,
+                                   vocab_size=WhisperConfig.from_pretrained(args.model_name_or_path).vocab_size,
                                    text_decoder=lambda ids: bytes(i for i in ids if i < 256).decode("utf-8", "ignore"))
+
+
+def special_tokens_for(tokenizer, model):
+    """The label side's special-token layout: the tokenizer's own table when it has one (the reference's
+    convert_tokens_to_ids, :1129), else the layout of the model's vocab_size."""
+    from .data import SpecialTokens
+    if getattr(tokenizer, "specials", None) is not None:
+        return tokenizer.specials
+    if hasattr(tokenizer, "convert_tokens_to_ids"):
+        return SpecialTokens.from_tokenizer(tokenizer)
+    return SpecialTokens.for_vocab(model.config.vocab_size)
 
 
 def _dist():
@@ -241,9 +255,20 @@ def main(argv=None):
                   "return_timestamps": args.return_timestamps and args.timestamp_probability > 0}
     if args.language is not None:
         gen_kwargs.update(language=args.language, task=args.task)
+    from .feature_extraction import WhisperFeatureExtractor
+    if teacher.config.vocab_size != student.config.vocab_size or \
+            teacher.config.num_mel_bins != student.config.num_mel_bins:
+        raise ValueError("teacher and student disagree on vocab_size / num_mel_bins: "
+                         f"{teacher.config.vocab_size}/{teacher.config.num_mel_bins} vs "
+                         f"{student.config.vocab_size}/{student.config.num_mel_bins}")
+    specials = special_tokens_for(tokenizer, student)
+    fe = WhisperFeatureExtractor.from_pretrained(args.model_name_or_path, device=dev)
+    if fe.feature_size != student.config.num_mel_bins:
+        raise ValueError(f"{args.model_name_or_path}: preprocessor feature_size {fe.feature_size} != "
+                         f"num_mel_bins {student.config.num_mel_bins}")
     prep = dict(timestamp_probability=args.timestamp_probability,
                 condition_on_prev_probability=args.condition_on_prev_probability,
-                max_label_length=args.max_label_length)
+                max_label_length=args.max_label_length, specials=specials, feature_extractor=fe)
 
     train_ds = CoolDataset(args.train_dataset_manifest, args.train_dataset_root) if args.do_train else None
     eval_ds = CoolDataset(args.eval_dataset_manifest, args.eval_dataset_root) if args.eval_dataset_manifest else None
@@ -291,7 +316,8 @@ def main(argv=None):
             if args.do_eval and eval_ds is not None and (cur_step % eval_steps == 0 or cur_step == total):
                 ef = DataFeed(eval_ds, tokenizer, args.per_device_eval_batch_size, rank=rank, world=world, device=dev,
                               seed=args.seed, shuffle=False, timestamp_probability=0.0,
-                              condition_on_prev_probability=0.0, max_label_length=args.max_label_length)
+                              condition_on_prev_probability=0.0, max_label_length=args.max_label_length,
+                              specials=specials, feature_extractor=fe)
                 em = evaluate(trainer, ef, tokenizer, gen_kwargs, args.predict_with_generate, world,
                               gen_kwargs["return_timestamps"])
                 em.update(step=cur_step)

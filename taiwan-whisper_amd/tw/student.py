@@ -124,7 +124,7 @@ def init_student_model_from_teacher(teacher_checkpoint, encoder_layers=None, dec
         if smoke_forward:   # :204-221 — reload and run one forward on np.ones(16000)
             st2 = WhisperForConditionalGeneration.from_pretrained(save_dir, device=device)
             from .feature_extraction import WhisperFeatureExtractor
-            fe = WhisperFeatureExtractor(device=device)
+            fe = WhisperFeatureExtractor(feature_size=st2.config.num_mel_bins, device=device)
             feats = fe(np.ones(16000))
             ids = torch.full((1, 1), st2.config.decoder_start_token_id, dtype=torch.long, device=device)
             st2(conv_input=feats.conv_input, decoder_input_ids=ids)

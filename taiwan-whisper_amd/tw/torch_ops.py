@@ -15,7 +15,7 @@ Arithmetic (autocast rounding points), reference call sites:
   tw::layer_norm        y = round16(LN(x)) (+ mean, rstd)                    nn.LayerNorm (fp32 statistics)
   tw::attention         o = softmax(q k^T * scale [causal]) v (+ lse)        SDPA (HF attention interface :337-350)
   tw::kl_ce             (loss, ce, kl), dloss/ds                              run_distillation.py:1507-1516, 1539-1549
-  tw::log_mel           [B, n] fp32 -> [B, 80, n // 160] fp32                  WhisperFeatureExtractor (HF :135-170)
+  tw::log_mel           [B, n] fp32 -> [B, 80|128, n // 160] fp32              WhisperFeatureExtractor (HF :135-170)
 Backward products use the same kernels as tw.modeling.Backward (bf16 dX / dW / bias sums, rounded as autocast rounds
 them); the 16-bit forward ops accept bf16 and fp16 (fp16: forward only, as the engine's fp16 model).
 """
@@ -285,25 +285,26 @@ kl_ce.register_autograd(_klce_bwd, setup_context=_klce_setup)
 
 # ------------------------------------------------------------------------------------------------ log-mel
 @functools.lru_cache(maxsize=None)
-def _mel_tables(device: str):
+def _mel_tables(device: str, n_mels: int = 80):
     from .feature_extraction import mel_tables
-    return mel_tables(device)
+    return mel_tables(device, n_mels)
 
 
 @torch.library.custom_op("tw::log_mel", mutates_args=(), device_types="cuda")
-def log_mel(wav: Tensor) -> Tensor:
-    """[B, n] fp32 waveform (16 kHz; n = 480 000 for a 30 s window, any n > 200 for long-form) -> [B, 80, n // 160]."""
+def log_mel(wav: Tensor, n_mels: int = 80) -> Tensor:
+    """[B, n] fp32 waveform (16 kHz; n = 480 000 for a 30 s window, any n > 200 for long-form) -> [B, n_mels, n // 160];
+    n_mels is 80, or 128 for the large-v3 family."""
     wav = wav.contiguous()
     B, n = wav.shape
-    basis, start, w = _mel_tables(str(wav.device))
-    mel = torch.empty(B, 80, n // 160, dtype=torch.float32, device=wav.device)
+    basis, start, w = _mel_tables(str(wav.device), n_mels)
+    mel = torch.empty(B, n_mels, n // 160, dtype=torch.float32, device=wav.device)
     F.logmel(wav, basis, start, w, mel)
     return mel
 
 
 @log_mel.register_fake
-def _(wav):
-    return wav.new_empty(wav.shape[0], 80, wav.shape[1] // 160)
+def _(wav, n_mels=80):
+    return wav.new_empty(wav.shape[0], n_mels, wav.shape[1] // 160)
 
 
 OPS = ("linear", "linear_gelu", "linear_residual", "layer_norm", "attention", "kl_ce", "log_mel")
