@@ -85,7 +85,10 @@ int tw_layernorm_bwd_ex(const void* x, int x_dtype, const float* w, const float*
                         float* workspace, int64_t workspace_floats, void* g16, int g_dtype, tw_stream_t stream);
 
 /* Flash attention, head_dim 64, bf16 (replaces SDPA at HF modeling_whisper.py:337-350 for encoder
- * self-attn, decoder causal self-attn and cross-attn).  lse: [B][H][Tq] fp32 (natural log). */
+ * self-attn, decoder causal self-attn and cross-attn).  lse: [B][H][Tq] fp32 (natural log).
+ * scale must be > 0: the forward takes each row's max on the raw scores before scaling, so every bf16 / fp16
+ * entry (tw_attn_fwd / _bwd, their _f16 and _varlen forms) returns TW_EINVAL for a zero, negative or NaN scale
+ * before any launch.  (tw_attn_*_f32 scales the scores in its GEMM and takes the max afterwards: any scale.) */
 int tw_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
                 int64_t ldo, float* lse, int B, int H, int Tq, int Tk, int head_dim, int causal, float scale,
                 tw_stream_t stream);

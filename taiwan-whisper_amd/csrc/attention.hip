@@ -600,6 +600,7 @@ extern "C" int tw_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ld
                            int64_t ldo, float* lse, int B, int H, int Tq, int Tk, int head_dim, int causal, float scale,
                            hipStream_t stream) {
   if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
   if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
   if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
   if (causal && Tq > Tk) return TW_EINVAL;
@@ -618,6 +619,7 @@ extern "C" int tw_attn_fwd_f16(const void* Q, int64_t ldq, const void* K, int64_
                                void* O, int64_t ldo, float* lse, int B, int H, int Tq, int Tk, int head_dim, int causal,
                                float scale, hipStream_t stream) {
   if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
   if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
   if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
   if (causal && Tq > Tk) return TW_EINVAL;
@@ -638,6 +640,7 @@ int attn_bwd_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const v
                  int64_t lddk, void* dV, int64_t lddv, int B, int H, int Tq, int Tk, int head_dim, int causal,
                  float scale, float* workspace, bool half, hipStream_t stream) {
   if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
   if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
   if (!check_common(Q, K, V, ldq, ldk, ldv) || ((uintptr_t)dO & 15) || (lddo & 7) || ((uintptr_t)O & 15) || (ldo & 7))
     return TW_EINVAL;
@@ -695,6 +698,7 @@ int attn_fwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, 
                         int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
                         int Tk, int head_dim, int causal, float scale, bool half, hipStream_t stream) {
   if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
   if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
   if (Mq == 0 || max_q == 0 || Tk == 0) return TW_OK;
   if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
@@ -718,6 +722,7 @@ int attn_bwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, 
                         int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
                         float* workspace, bool half, hipStream_t stream) {
   if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
   if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
   if (Tk == 0) return TW_OK;
   if (!check_common(Q, K, V, ldq, ldk, ldv) || ((uintptr_t)dO & 15) || (lddo & 7) || ((uintptr_t)O & 15) || (ldo & 7))
