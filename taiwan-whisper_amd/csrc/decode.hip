@@ -30,41 +30,59 @@ namespace {
 
 using namespace twd;
 
+// effective key count of a call: the fixed Tk plus the device-side step index, bounded by the score buffer
+__device__ __forceinline__ int eff_tk(const DecP& p) { return min(p.Tk + (p.tk_dev ? *p.tk_dev : 0), DA_MAX_TK); }
+
+// per-row key start (left-padded decoder prompts: HF's decoder attention mask): row b attends keys
+// [k_start[b], tk), the start clamped into [0, tk - 1] so at least the last key -- the step's own -- is used and no
+// row below 0 or at / past tk is read.  The body walks from lo, so row b's result is bit-identical to the plain
+// call run on that row alone with K / V advanced by k_start[b] rows over tk - k_start[b] keys; without k_start
+// every row starts at key 0.  The single-query kernels take the choice as a template argument (KS): with a
+// run-time test of p.k_start the plain one-workgroup kernel measured 174 -> 186 us at 128 clips x 20 heads
+// (profiles/decode_refactor_ab.txt), so the KS = false instantiations are the kernels without the feature.
+__device__ __forceinline__ int clamp_start(const int* k_start, int b, int tk) {
+  return max(min(k_start[b], tk - 1), 0);
+}
+
+// the partial of a chunk that holds none of a query's keys (m = -inf, l = 0): the combine kernels skip it
+__device__ __forceinline__ void store_empty_partial(float* part) {
+  if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
+  if (threadIdx.x == 0) {
+    part[64] = -INFINITY;
+    part[65] = 0.f;
+  }
+}
+
 // U = loads in flight per lane, K/V streamed with nontemporal loads (round 4, tools/bench_decode_attn.py, same box,
 // profiles/r04_uv_decode_attn_ab.log): at the c4 shape (fp16, 512 clips x 20 heads over 1500 frames) U = 4 plain
 // 665 us, U = 4 nontemporal 620, U = 2 nontemporal 609 (6.45 TB/s), U = 8 782 (occupancy); at 128 x 20 pairs
 // U = 4 nontemporal 168 vs U = 2 190 -- hence U = 2 from DA_BIG pairs.
-template <typename E, int U>
+template <typename E, int U, bool KS>
 __device__ __forceinline__ void decode_attn_pair(const DecP& p) {
   const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
-  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
-  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
-  decode_attn_body<E, U, true>(p, b, h, 0, tk, nullptr);
+  const int tk = eff_tk(p);
+  decode_attn_body<E, U, true>(p, b, h, KS ? clamp_start(p.k_start, b, tk) : 0, tk, nullptr);
 }
-template <typename E>
-__global__ __launch_bounds__(DA_THREADS) void decode_attn_u4_kernel(DecP p) { decode_attn_pair<E, 4>(p); }
-template <typename E>
-__global__ __launch_bounds__(DA_THREADS) void decode_attn_u2_kernel(DecP p) { decode_attn_pair<E, 2>(p); }
+template <typename E, bool KS>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_u4_kernel(DecP p) { decode_attn_pair<E, 4, KS>(p); }
+template <typename E, bool KS>
+__global__ __launch_bounds__(DA_THREADS) void decode_attn_u2_kernel(DecP p) { decode_attn_pair<E, 2, KS>(p); }
 
-// split over keys (few (clip, head) pairs: batch-1 long-form): blockIdx.y = chunk of S keys; chunks past
-// the effective Tk store an empty partial (m = -inf, l = 0); decode_attn_combine_kernel merges them.
+// split over keys (few (clip, head) pairs: batch-1 long-form): blockIdx.y = chunk of S keys; a chunk past the
+// effective Tk or wholly below the row's start stores an empty partial, the chunk the start falls into begins
+// there; decode_attn_combine_kernel merges them.
 // (Tried, r02: the last-arriving chunk combining in place -- agent-scope release + arrival counter --
 // saves the second launch at batch 1 (14.6 -> 13.7 us) but every workgroup's release writes back the
 // whole L2: 27 -> 202 us at B = 16, and c5 measured no faster.  Two launches it is.)
-template <typename E>
+template <typename E, bool KS>
 __global__ __launch_bounds__(DA_THREADS) void decode_attn_split_kernel(DecP p, int S, float* ws) {
   const int bh = blockIdx.x, c = blockIdx.y;
   const int b = bh / p.H, h = bh % p.H;
-  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
-  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
+  const int tk = eff_tk(p);
   float* part = ws + ((int64_t)bh * gridDim.y + c) * 66;
-  const int lo = c * S, hi = min(tk, lo + S);
+  const int lo = KS ? max(c * S, clamp_start(p.k_start, b, tk)) : c * S, hi = min(tk, c * S + S);
   if (lo >= hi) {
-    if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
-    if (threadIdx.x == 0) {
-      part[64] = -INFINITY;
-      part[65] = 0.f;
-    }
+    store_empty_partial(part);
     return;
   }
   decode_attn_body<E>(p, b, h, lo, hi, part);
@@ -75,61 +93,15 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecP p, int nch
   combine_row<E>(p, blockIdx.x, nchunk, ws + (int64_t)blockIdx.x * nchunk * 66);
 }
 
-// per-row key start (left-padded decoder prompts: HF's decoder attention mask): row b attends keys
-// [k_start[b], tk), the start clamped into [0, tk - 1] so at least the last key -- the step's own -- is used and no
-// row below 0 or at / past tk is read.  The body walks from lo, so row b's result is bit-identical to the plain
-// kernel run on that row alone with K / V advanced by k_start[b] rows over tk - k_start[b] keys.
-__device__ __forceinline__ int clamp_start(const int* k_start, int b, int tk) {
-  return max(min(k_start[b], tk - 1), 0);
-}
-template <typename E, int U>
-__device__ __forceinline__ void decode_attn_pair_ks(const DecP& p, const int* k_start) {
-  const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
-  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
-  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
-  decode_attn_body<E, U, true>(p, b, h, clamp_start(k_start, b, tk), tk, nullptr);
-}
-template <typename E>
-__global__ __launch_bounds__(DA_THREADS) void decode_attn_ks_u4_kernel(DecP p, const int* __restrict__ k_start) {
-  decode_attn_pair_ks<E, 4>(p, k_start);
-}
-template <typename E>
-__global__ __launch_bounds__(DA_THREADS) void decode_attn_ks_u2_kernel(DecP p, const int* __restrict__ k_start) {
-  decode_attn_pair_ks<E, 2>(p, k_start);
-}
-
-// the split variant: a chunk wholly below the row's start stores the empty partial, as a chunk past tk does; the
-// chunk the start falls into begins there
-template <typename E>
-__global__ __launch_bounds__(DA_THREADS) void decode_attn_split_ks_kernel(DecP p, int S, float* ws,
-                                                                          const int* __restrict__ k_start) {
-  const int bh = blockIdx.x, c = blockIdx.y;
-  const int b = bh / p.H, h = bh % p.H;
-  int tk = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
-  if (tk > DA_MAX_TK) tk = DA_MAX_TK;
-  float* part = ws + ((int64_t)bh * gridDim.y + c) * 66;
-  const int lo = max(c * S, clamp_start(k_start, b, tk)), hi = min(tk, c * S + S);
-  if (lo >= hi) {
-    if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
-    if (threadIdx.x == 0) {
-      part[64] = -INFINITY;
-      part[65] = 0.f;
-    }
-    return;
-  }
-  decode_attn_body<E>(p, b, h, lo, hi, part);
-}
-
 // Multi-query decode attention (tw_decode_attn_mq: the verify pass of assisted decoding).  nq <= QN query rows per
 // (clip, head); query j attends keys [start_j, tk_j), tk_j = Tk (+ *tk_dev) (+ j when causal), start_j the row's
-// k_start clamped into [0, tk_j - 1] as tw_decode_attn_ks clamps it.  The queries that share a start -- all of them
+// k_start clamped into [0, tk_j - 1] (clamp_start).  The queries that share a start -- all of them
 // unless the start reaches a query's limit -- go through decode_attn_body_mq together (each K / V row loaded once);
 // a query whose clamped start differs walks the keys from its own start, as its single-query call does, in a
 // pass of its own.
 struct MqP {
   int64_t sqq, soq;
   int nq, causal;
-  const int* k_start;
 };
 template <int QN>
 __device__ __forceinline__ void mq_group(unsigned& pend, const int (&lo)[QN], const int (&hi)[QN], int& glo,
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_kernel(DecP p, MqP 
   __shared__ float sc[DA_MQ_LDS];
   constexpr int cap = DA_MQ_LDS / QN > DA_MAX_TK ? DA_MAX_TK : DA_MQ_LDS / QN;
   const int b = blockIdx.x / p.H, h = blockIdx.x % p.H;
-  const int tk0 = p.Tk + (p.tk_dev ? *p.tk_dev : 0);
+  const int tk0 = eff_tk(p);
   int lo[QN], hi[QN];
   unsigned pend = 0;
 #pragma unroll
@@ -159,7 +131,7 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_kernel(DecP p, MqP 
     lo[j] = hi[j] = 0;
     if (j < q.nq) {
       const int tk = min(tk0 + (q.causal ? j : 0), DA_MAX_TK);
-      lo[j] = q.k_start ? clamp_start(q.k_start, b, tk) : 0;
+      lo[j] = p.k_start ? clamp_start(p.k_start, b, tk) : 0;
       hi[j] = min(tk, lo[j] + cap);
       if (hi[j] > lo[j]) pend |= 1u << j;
     }
@@ -186,19 +158,11 @@ __global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_split_kernel(DecP p
   for (int j = 0; j < QN; ++j) {
     lo[j] = hi[j] = 0;
     if (j < q.nq) {
-      const int tk = min(p.Tk + (q.causal ? j : 0), DA_MAX_TK);
-      lo[j] = max(c * DA_SPLIT, q.k_start ? clamp_start(q.k_start, b, tk) : 0);
+      const int tk = min(eff_tk(p) + (q.causal ? j : 0), DA_MAX_TK);
+      lo[j] = max(c * DA_SPLIT, p.k_start ? clamp_start(p.k_start, b, tk) : 0);
       hi[j] = min(tk, c * DA_SPLIT + DA_SPLIT);
-      if (hi[j] > lo[j]) {
-        pend |= 1u << j;
-      } else {                                           // chunk past the query's keys or below its start: empty
-        float* pj = part + j * pstride;
-        if (threadIdx.x < 64) pj[threadIdx.x] = 0.f;
-        if (threadIdx.x == 0) {
-          pj[64] = -INFINITY;
-          pj[65] = 0.f;
-        }
-      }
+      if (hi[j] > lo[j]) pend |= 1u << j;
+      else store_empty_partial(part + j * pstride);        // chunk past the query's keys or below its start
     }
   }
   while (pend) {
@@ -773,14 +737,17 @@ int sel_vec(const void* logits, int64_t ld, int V) {
   return ((uintptr_t)logits % 16 == 0 && ld % 8 == 0 && ld >= (int64_t)((V + 7) / 8) * 8) ? 1 : 0;
 }
 
-// launch K<bf16> or K<float> by the logits dtype code
-#define TW_LAUNCH_DT(dt, K, grid, block, ...)                                              \
-  do {                                                                                      \
-    if ((dt) == TW_BF16) hipLaunchKernelGGL(K<bf16>, grid, block, 0, stream, __VA_ARGS__);   \
-    else if ((dt) == TW_F16) hipLaunchKernelGGL(K<f16>, grid, block, 0, stream, __VA_ARGS__);  \
-    else if ((dt) == TW_F32) hipLaunchKernelGGL(K<float>, grid, block, 0, stream, __VA_ARGS__); \
-    else return TW_EUNSUPPORTED;                                                            \
+// run the statement with E = the element type of a dtype code: TW_DISPATCH_DT(dt, hipLaunchKernelGGL(K<E>, ...))
+#define TW_DISPATCH_DT(dt, ...)                              \
+  do {                                                       \
+    if ((dt) == TW_BF16) { using E = bf16; __VA_ARGS__; }    \
+    else if ((dt) == TW_F16) { using E = f16; __VA_ARGS__; } \
+    else if ((dt) == TW_F32) { using E = float; __VA_ARGS__; } \
+    else return TW_EUNSUPPORTED;                             \
   } while (0)
+// launch K<bf16>, K<f16> or K<float> by the dtype code
+#define TW_LAUNCH_DT(dt, K, grid, block, ...) \
+  TW_DISPATCH_DT(dt, hipLaunchKernelGGL(K<E>, grid, block, 0, stream, __VA_ARGS__))
 
 // slices per row: enough workgroups to cover the chip for a handful of rows, one per row from 256 rows
 // up; the slices are multiples of 8 ids (for_row's 16-B chunks)
@@ -791,29 +758,119 @@ int sel_slices(int B, int V) {
   return (V + slice - 1) / slice;
 }
 
-int launch_select(const SelP& p, int B, int logits_dtype, hipStream_t stream) {
-  const int G = sel_slices(B, p.V);
-  const int slice = ((p.V + G - 1) / G + 7) / 8 * 8;
+// the scan and merge kernels of the two selection families (plain / timestamp rules) and the merge's block size
+struct GreedyK {
+  template <typename E> static constexpr auto scan = greedy_select_kernel<E>;
+  template <typename E> static constexpr auto merge = greedy_merge_kernel<E>;
+  static constexpr int merge_block = 64;
+};
+struct TsK {
+  template <typename E> static constexpr auto scan = greedy_select_ts_kernel<E>;
+  template <typename E> static constexpr auto merge = ts_merge_kernel<E>;
+  static constexpr int merge_block = 256;
+};
+template <class K, class P>
+int launch_select(const P& p, int B, int V, int logits_dtype, hipStream_t stream) {
+  const int G = sel_slices(B, V);
+  const int slice = ((V + G - 1) / G + 7) / 8 * 8;
   float* ws = G > 1 ? (float*)tw_device_workspace(stream, (size_t)B * G * SEL_WORDS * sizeof(float)) : nullptr;
   if (G > 1 && ws) {
-    TW_LAUNCH_DT(logits_dtype, greedy_select_kernel, dim3(G, B), dim3(256), p, slice, ws);
-    TW_LAUNCH_DT(logits_dtype, greedy_merge_kernel, dim3(B), dim3(64), p, G, ws);
+    TW_LAUNCH_DT(logits_dtype, K::template scan, dim3(G, B), dim3(256), p, slice, ws);
+    TW_LAUNCH_DT(logits_dtype, K::template merge, dim3(B), dim3(K::merge_block), p, G, ws);
   } else {
-    TW_LAUNCH_DT(logits_dtype, greedy_select_kernel, dim3(1, B), dim3(256), p, p.V, (float*)nullptr);
+    TW_LAUNCH_DT(logits_dtype, K::template scan, dim3(1, B), dim3(256), p, V, (float*)nullptr);
   }
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
 
-int launch_select_ts(const SelTsP& q, int B, int logits_dtype, hipStream_t stream) {
-  const int G = sel_slices(B, q.s.V);
-  const int slice = ((q.s.V + G - 1) / G + 7) / 8 * 8;
-  float* ws = G > 1 ? (float*)tw_device_workspace(stream, (size_t)B * G * SEL_WORDS * sizeof(float)) : nullptr;
-  if (G > 1 && ws) {
-    TW_LAUNCH_DT(logits_dtype, greedy_select_ts_kernel, dim3(G, B), dim3(256), q, slice, ws);
-    TW_LAUNCH_DT(logits_dtype, ts_merge_kernel, dim3(B), dim3(256), q, G, ws);
+// the argument checks every selection entry point makes, and the SelP of the call
+bool sel_bad(int64_t ld, int V, const uint8_t* done, const int64_t* ids, const int64_t* next_ids) {
+  return V <= 0 || ld < V || !done || !ids || !next_ids;
+}
+SelP sel_fill(const void* logits, int64_t ld, int V, const uint32_t* suppress_bits, const uint32_t* begin_bits,
+              int apply_begin, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids, int col, int64_t* next_ids,
+              const int* t_dev, int begin_col, const uint32_t* ctl, float* sum_logp) {
+  SelP p;
+  p.logits = logits; p.ld = ld; p.V = V;
+  p.suppress = suppress_bits; p.begin = begin_bits; p.apply_begin = apply_begin;
+  p.eos = eos; p.done = done; p.ids = ids; p.ld_ids = ld_ids; p.col = col; p.next = next_ids;
+  p.t_dev = t_dev; p.begin_col = begin_col;
+  p.ctl = ctl; p.sum_logp = sum_logp; p.vec = sel_vec(logits, ld, V);
+  return p;
+}
+
+// The checks the decode-attention entry points share (statuses as include/tw_hip.h lists them) and the DecP of the
+// call.  tk_last: the most keys a query of a fixed-Tk call attends.
+int dec_fill(DecP& p, const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk, const void* v,
+             int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int H, int Tk, int tk_last,
+             const int* tk_dev, const int* k_start, float scale) {
+  if ((!tk_dev && Tk <= 0) || tk_last > DA_MAX_TK) return TW_EUNSUPPORTED;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
+  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
+  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
+  p.q = q; p.sqb = sqb;
+  p.k = k; p.ldk = ldk; p.skb = skb;
+  p.v = v; p.ldv = ldv; p.svb = svb;
+  p.o = o; p.sob = sob;
+  p.hsk = hsk; p.hsv = hsv;
+  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.k_start = k_start; p.c = scale * 1.4426950408889634f;
+  return TW_OK;
+}
+// fixed-Tk calls on few (clip, head) pairs split the keys into chunks of DA_SPLIT (decode_attn below)
+bool dec_split(const int* tk_dev, int pairs, int nchunk) {
+  return !tk_dev && pairs < 640 && nchunk >= 2 && nchunk <= DA_MAX_CHUNK;
+}
+
+// launch K<E, true> when the call has a per-row key start, K<E, false> when not
+#define DEC_LAUNCH_KS(K, grid, ...)                                                                          \
+  do {                                                                                                       \
+    if (p.k_start) TW_DISPATCH_DT(dtype, hipLaunchKernelGGL((K<E, true>), grid, dim3(DA_THREADS), 0, stream, __VA_ARGS__));  \
+    else TW_DISPATCH_DT(dtype, hipLaunchKernelGGL((K<E, false>), grid, dim3(DA_THREADS), 0, stream, __VA_ARGS__));           \
+  } while (0)
+
+// tw_decode_attn / _hs / _ks: k_start null for the first two
+int decode_attn(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk, const void* v,
+                int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B, int H, int Tk, const int* tk_dev,
+                const int* k_start, int head_dim, float scale, int dtype, hipStream_t stream) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  if (B <= 0 || H <= 0) return TW_OK;
+  DecP p;
+  if (const int st = dec_fill(p, q, sqb, k, ldk, skb, hsk, v, ldv, svb, hsv, o, sob, H, Tk, Tk, tk_dev, k_start, scale))
+    return st;
+  // few (clip, head) pairs (batch-1 long-form, small batches): split the keys into chunks of DA_SPLIT over
+  // the grid's y dimension, then combine.  Measured (tools/bench_decode_attn.py, H = 20, Tk = 1500): B = 1
+  // 26.9 -> 14.6 us, B = 16 46.9 -> 31.2 us; from B = 64 (1280 pairs) the one-workgroup-per-pair kernel is
+  // faster (90.6 vs 114.8 us).  With tk_dev (self-attention over a graph-captured cache) the host does
+  // not know Tk, so the chunks would have to cover the kernel's DA_MAX_TK bound: measured on c5 (batch-1
+  // long-form, Tk <= 448) that costs more than it saves (2.75 -> 2.93 ms per decode step), so only fixed-Tk calls
+  // below 640 pairs split.
+  const int nchunk = (Tk + DA_SPLIT - 1) / DA_SPLIT;
+  if (dec_split(tk_dev, B * H, nchunk)) {
+    float* ws = (float*)tw_device_workspace(stream, (size_t)B * H * nchunk * 66 * sizeof(float));
+    if (ws) {
+      DEC_LAUNCH_KS(decode_attn_split_kernel, dim3(B * H, nchunk), p, DA_SPLIT, ws);
+      TW_LAUNCH_DT(dtype, decode_attn_combine_kernel, dim3(B * H), dim3(64), p, nchunk, ws);
+      TW_CHECK_LAUNCH();
+      return TW_OK;
+    }
+  }
+  if (B * H >= DA_BIG) DEC_LAUNCH_KS(decode_attn_u2_kernel, dim3(B * H), p);
+  else DEC_LAUNCH_KS(decode_attn_u4_kernel, dim3(B * H), p);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+template <int QN>
+int launch_mq(const DecP& p, const MqP& q, int B, int nchunk, bool split, int dtype, hipStream_t stream) {
+  float* ws = split ? (float*)tw_device_workspace(stream, (size_t)B * p.H * q.nq * nchunk * 66 * sizeof(float)) : nullptr;
+  if (ws) {
+    TW_DISPATCH_DT(dtype, hipLaunchKernelGGL((decode_attn_mq_split_kernel<E, QN>), dim3(B * p.H, nchunk),
+                                             dim3(DA_THREADS), 0, stream, p, q, ws));
+    TW_LAUNCH_DT(dtype, decode_attn_mq_combine_kernel, dim3(B * p.H * q.nq), dim3(64), p, q, nchunk, ws);
   } else {
-    TW_LAUNCH_DT(logits_dtype, greedy_select_ts_kernel, dim3(1, B), dim3(256), q, q.s.V, (float*)nullptr);
+    TW_DISPATCH_DT(dtype, hipLaunchKernelGGL((decode_attn_mq_kernel<E, QN>), dim3(B * p.H), dim3(DA_THREADS), 0,
+                                             stream, p, q));
   }
   TW_CHECK_LAUNCH();
   return TW_OK;
@@ -821,20 +878,29 @@ int launch_select_ts(const SelTsP& q, int B, int logits_dtype, hipStream_t strea
 
 }  // namespace
 
+namespace {
+// tw_greedy_select_ts (ctl, sum_logp null) and tw_select_sample_ts
+int select_ts(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
+              const uint32_t* begin_bits, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids,
+              int col, int64_t* next_ids, const int* t_dev, int begin_col, int ts_begin,
+              int no_ts, int max_initial, int* last_ts, const uint32_t* ctl,
+              float* sum_logp, hipStream_t stream) {
+  if (sel_bad(ld, V, done, ids, next_ids) || !last_ts || ts_begin <= eos || ts_begin > V) return TW_EINVAL;
+  SelTsP q;
+  q.s = sel_fill(logits, ld, V, suppress_bits, begin_bits, 0, eos, done, ids, ld_ids, col, next_ids, t_dev, begin_col,
+                 ctl, sum_logp);
+  q.begin_col = begin_col; q.ts_begin = ts_begin; q.no_ts = no_ts; q.max_initial = max_initial; q.last_ts = last_ts;
+  return launch_select<TsK>(q, B, V, logits_dtype, stream);
+}
+}  // namespace
+
 extern "C" int tw_greedy_select_ts(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
                                    const uint32_t* begin_bits, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids,
                                    int col, int64_t* next_ids, const int* t_dev, int begin_col, int ts_begin,
                                    int no_ts, int max_initial, int* last_ts, hipStream_t stream) {
   if (B <= 0) return TW_OK;
-  if (V <= 0 || ld < V || !done || !ids || !next_ids || !last_ts || ts_begin <= eos || ts_begin > V) return TW_EINVAL;
-  SelTsP q;
-  q.s.logits = logits; q.s.ld = ld; q.s.V = V;
-  q.s.suppress = suppress_bits; q.s.begin = begin_bits; q.s.apply_begin = 0;
-  q.s.eos = eos; q.s.done = done; q.s.ids = ids; q.s.ld_ids = ld_ids; q.s.col = col; q.s.next = next_ids;
-  q.s.t_dev = t_dev; q.s.begin_col = begin_col;
-  q.s.ctl = nullptr; q.s.sum_logp = nullptr; q.s.vec = sel_vec(logits, ld, V);
-  q.begin_col = begin_col; q.ts_begin = ts_begin; q.no_ts = no_ts; q.max_initial = max_initial; q.last_ts = last_ts;
-  return launch_select_ts(q, B, logits_dtype, stream);
+  return select_ts(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, eos, done, ids, ld_ids, col, next_ids,
+                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, nullptr, nullptr, stream);
 }
 
 extern "C" int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
@@ -843,31 +909,16 @@ extern "C" int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dt
                                    int no_ts, int max_initial, int* last_ts, const uint32_t* ctl, float* sum_logp,
                                    hipStream_t stream) {
   if (B <= 0) return TW_OK;
-  if (V <= 0 || ld < V || !done || !ids || !next_ids || !last_ts || ts_begin <= eos || ts_begin > V) return TW_EINVAL;
   if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
-  SelTsP q;
-  q.s.logits = logits; q.s.ld = ld; q.s.V = V;
-  q.s.suppress = suppress_bits; q.s.begin = begin_bits; q.s.apply_begin = 0;
-  q.s.eos = eos; q.s.done = done; q.s.ids = ids; q.s.ld_ids = ld_ids; q.s.col = col; q.s.next = next_ids;
-  q.s.t_dev = t_dev; q.s.begin_col = begin_col;
-  q.s.ctl = ctl; q.s.sum_logp = sum_logp; q.s.vec = sel_vec(logits, ld, V);
-  q.begin_col = begin_col; q.ts_begin = ts_begin; q.no_ts = no_ts; q.max_initial = max_initial; q.last_ts = last_ts;
-  return launch_select_ts(q, B, logits_dtype, stream);
+  return select_ts(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, eos, done, ids, ld_ids, col, next_ids,
+                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, ctl, sum_logp, stream);
 }
 
 extern "C" int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, int V, int token,
                                 float* out, hipStream_t stream) {
   if (B <= 0) return TW_OK;
   if (V <= 0 || ld < V || token < 0 || token >= V || !out) return TW_EINVAL;
-  if (logits_dtype == TW_BF16)
-    hipLaunchKernelGGL(token_logprob_kernel<bf16>, dim3(B), dim3(256), 0, stream, (const bf16*)logits, ld, V, token, out);
-  else if (logits_dtype == TW_F16)
-    hipLaunchKernelGGL(token_logprob_kernel<f16>, dim3(B), dim3(256), 0, stream, (const f16*)logits, ld, V, token, out);
-  else if (logits_dtype == TW_F32)
-    hipLaunchKernelGGL(token_logprob_kernel<float>, dim3(B), dim3(256), 0, stream, (const float*)logits, ld, V, token,
-                       out);
-  else
-    return TW_EUNSUPPORTED;
+  TW_LAUNCH_DT(logits_dtype, token_logprob_kernel, dim3(B), dim3(256), (const E*)logits, ld, V, token, out);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -920,14 +971,9 @@ extern "C" int tw_kv_head_major(const void* src, int64_t ld, void* dst, int B, i
   const int64_t rows = (int64_t)B * Tk;
   const int64_t nvec = rows * (2 * 64 * H) / (w + 1);
   const dim3 grid((unsigned)std::min<int64_t>((nvec + 255) / 256, 16384));
-  if (dtype == TW_BF16 || dtype == TW_F16)
-    hipLaunchKernelGGL(kv_head_major_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)src, ld, (bf16*)dst, Tk, H,
-                       rows);
-  else if (dtype == TW_F32)
-    hipLaunchKernelGGL(kv_head_major_kernel<float>, grid, dim3(256), 0, stream, (const float*)src, ld, (float*)dst,
-                       Tk, H, rows);
-  else
-    return TW_EUNSUPPORTED;
+  // a copy: the 16-bit types move as bf16
+  TW_LAUNCH_DT(dtype == TW_F16 ? TW_BF16 : dtype, kv_head_major_kernel, grid, dim3(256), (const E*)src, ld, (E*)dst, Tk,
+               H, rows);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -938,14 +984,9 @@ extern "C" int tw_kv_append(const void* src, int64_t ld_src, void* cache, int64_
   const int w = dtype == TW_F32 ? 3 : 7;          // 16-B vectors: 4 fp32 / 8 bf16
   if (!t_dev || (n & w) || (ld_src & w) || (ld_row & w) || (sb & w) || (((uintptr_t)src | (uintptr_t)cache) & 15))
     return TW_EINVAL;
-  if (dtype == TW_BF16 || dtype == TW_F16)
-    hipLaunchKernelGGL(kv_append_kernel<bf16>, dim3((n / 8 + 255) / 256, B), dim3(256), 0, stream, (const bf16*)src,
-                       ld_src, (bf16*)cache, ld_row, sb, n, t_dev);
-  else if (dtype == TW_F32)
-    hipLaunchKernelGGL(kv_append_kernel<float>, dim3((n / 4 + 255) / 256, B), dim3(256), 0, stream, (const float*)src,
-                       ld_src, (float*)cache, ld_row, sb, n, t_dev);
-  else
-    return TW_EUNSUPPORTED;
+  // a copy: the 16-bit types move as bf16
+  TW_LAUNCH_DT(dtype == TW_F16 ? TW_BF16 : dtype, kv_append_kernel, dim3((n / (w + 1) + 255) / 256, B), dim3(256),
+               (const E*)src, ld_src, (E*)cache, ld_row, sb, n, t_dev);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -961,120 +1002,26 @@ extern "C" int tw_decode_attn_hs(const void* q, int64_t sqb, const void* k, int6
                                  const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B,
                                  int H, int Tk, const int* tk_dev, int head_dim, float scale, int dtype,
                                  hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (B <= 0 || H <= 0) return TW_OK;
-  if ((!tk_dev && Tk <= 0) || Tk > DA_MAX_TK) return TW_EUNSUPPORTED;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
-  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
-  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
-  DecP p;
-  if (dtype == TW_F32 && ((sqb | ldk | skb | ldv | svb) & 3)) return TW_EINVAL;
-  p.q = q; p.sqb = sqb;
-  p.k = k; p.ldk = ldk; p.skb = skb;
-  p.v = v; p.ldv = ldv; p.svb = svb;
-  p.o = o; p.sob = sob;
-  p.hsk = hsk; p.hsv = hsv;
-  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.c = scale * 1.4426950408889634f;
-  // few (clip, head) pairs (batch-1 long-form, small batches): split the keys into chunks of DA_SPLIT over
-  // the grid's y dimension, then combine.  Measured (tools/bench_decode_attn.py, H = 20, Tk = 1500): B = 1
-  // 26.9 -> 14.6 us, B = 16 46.9 -> 31.2 us; from B = 64 (1280 pairs) the one-workgroup-per-pair kernel is
-  // faster (90.6 vs 114.8 us).  With tk_dev (self-attention over a graph-captured cache) the host does
-  // not know Tk, so the chunks would have to cover the kernel's DA_MAX_TK bound: measured on c5 (batch-1
-  // long-form, Tk <= 448) that costs more than it saves (2.75 -> 2.93 ms per decode step), so only fixed-Tk calls
-  // below 640 pairs split.
-  const int nchunk = (Tk + DA_SPLIT - 1) / DA_SPLIT;
-  const bool split = !tk_dev && B * H < 640;
-  if (split && nchunk >= 2 && nchunk <= DA_MAX_CHUNK) {
-    float* ws = (float*)tw_device_workspace(stream, (size_t)B * H * nchunk * 66 * sizeof(float));
-    if (ws) {
-      TW_LAUNCH_DT(dtype, decode_attn_split_kernel, dim3(B * H, nchunk), dim3(DA_THREADS), p, DA_SPLIT, ws);
-      TW_LAUNCH_DT(dtype, decode_attn_combine_kernel, dim3(B * H), dim3(64), p, nchunk, ws);
-      TW_CHECK_LAUNCH();
-      return TW_OK;
-    }
-  }
-  if (B * H >= DA_BIG) TW_LAUNCH_DT(dtype, decode_attn_u2_kernel, dim3(B * H), dim3(DA_THREADS), p);
-  else TW_LAUNCH_DT(dtype, decode_attn_u4_kernel, dim3(B * H), dim3(DA_THREADS), p);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
+  return decode_attn(q, sqb, k, ldk, skb, hsk, v, ldv, svb, hsv, o, sob, B, H, Tk, tk_dev, nullptr, head_dim, scale,
+                     dtype, stream);
 }
 
 extern "C" int tw_decode_attn(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, const void* v,
                               int64_t ldv, int64_t svb, void* o, int64_t sob, int B, int H, int Tk, const int* tk_dev,
                               int head_dim, float scale, int dtype, hipStream_t stream) {
-  return tw_decode_attn_hs(q, sqb, k, ldk, skb, 64, v, ldv, svb, 64, o, sob, B, H, Tk, tk_dev, head_dim, scale, dtype,
-                           stream);
+  return decode_attn(q, sqb, k, ldk, skb, 64, v, ldv, svb, 64, o, sob, B, H, Tk, tk_dev, nullptr, head_dim, scale,
+                     dtype, stream);
 }
 
-// tw_decode_attn_hs with a per-row key start: the same argument checks and the same choice between the split and
-// the one-workgroup-per-pair kernels, so a call with every start 0 computes what tw_decode_attn_hs computes
+// tw_decode_attn_hs with a per-row key start: a call with every start 0 computes what tw_decode_attn_hs computes
 extern "C" int tw_decode_attn_ks(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
                                  const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int B,
                                  int H, int Tk, const int* tk_dev, const int* k_start, int head_dim, float scale,
                                  int dtype, hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (B <= 0 || H <= 0) return TW_OK;
-  if (!k_start) return TW_EINVAL;
-  if ((!tk_dev && Tk <= 0) || Tk > DA_MAX_TK) return TW_EUNSUPPORTED;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
-  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
-  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
-  DecP p;
-  if (dtype == TW_F32 && ((sqb | ldk | skb | ldv | svb) & 3)) return TW_EINVAL;
-  p.q = q; p.sqb = sqb;
-  p.k = k; p.ldk = ldk; p.skb = skb;
-  p.v = v; p.ldv = ldv; p.svb = svb;
-  p.o = o; p.sob = sob;
-  p.hsk = hsk; p.hsv = hsv;
-  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.c = scale * 1.4426950408889634f;
-  const int nchunk = (Tk + DA_SPLIT - 1) / DA_SPLIT;
-  const bool split = !tk_dev && B * H < 640;
-  if (split && nchunk >= 2 && nchunk <= DA_MAX_CHUNK) {
-    float* ws = (float*)tw_device_workspace(stream, (size_t)B * H * nchunk * 66 * sizeof(float));
-    if (ws) {
-      TW_LAUNCH_DT(dtype, decode_attn_split_ks_kernel, dim3(B * H, nchunk), dim3(DA_THREADS), p, DA_SPLIT, ws,
-                   k_start);
-      TW_LAUNCH_DT(dtype, decode_attn_combine_kernel, dim3(B * H), dim3(64), p, nchunk, ws);
-      TW_CHECK_LAUNCH();
-      return TW_OK;
-    }
-  }
-  if (B * H >= DA_BIG) TW_LAUNCH_DT(dtype, decode_attn_ks_u2_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
-  else TW_LAUNCH_DT(dtype, decode_attn_ks_u4_kernel, dim3(B * H), dim3(DA_THREADS), p, k_start);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
+  if (!k_start && head_dim == 64 && B > 0 && H > 0) return TW_EINVAL;
+  return decode_attn(q, sqb, k, ldk, skb, hsk, v, ldv, svb, hsv, o, sob, B, H, Tk, tk_dev, k_start, head_dim, scale,
+                     dtype, stream);
 }
-
-namespace {
-template <int QN>
-int launch_mq(const DecP& p, const MqP& q, int B, int nchunk, bool split, int dtype, hipStream_t stream) {
-  if (split) {
-    float* ws = (float*)tw_device_workspace(stream, (size_t)B * p.H * q.nq * nchunk * 66 * sizeof(float));
-    if (ws) {
-      if (dtype == TW_BF16) {
-        hipLaunchKernelGGL((decode_attn_mq_split_kernel<bf16, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
-        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<bf16>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
-      } else if (dtype == TW_F16) {
-        hipLaunchKernelGGL((decode_attn_mq_split_kernel<f16, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
-        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<f16>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
-      } else {
-        hipLaunchKernelGGL((decode_attn_mq_split_kernel<float, QN>), dim3(B * p.H, nchunk), dim3(DA_THREADS), 0, stream, p, q, ws);
-        hipLaunchKernelGGL(decode_attn_mq_combine_kernel<float>, dim3(B * p.H * q.nq), dim3(64), 0, stream, p, q, nchunk, ws);
-      }
-      TW_CHECK_LAUNCH();
-      return TW_OK;
-    }
-  }
-  if (dtype == TW_BF16)
-    hipLaunchKernelGGL((decode_attn_mq_kernel<bf16, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
-  else if (dtype == TW_F16)
-    hipLaunchKernelGGL((decode_attn_mq_kernel<f16, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
-  else
-    hipLaunchKernelGGL((decode_attn_mq_kernel<float, QN>), dim3(B * p.H), dim3(DA_THREADS), 0, stream, p, q);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
-}
-}  // namespace
 
 // tw_decode_attn_ks for Q consecutive query rows per batch row: the same argument checks, the same split rule (the
 // (row, head) pairs counted as for one step, the chunks from the last query's key count), the same bodies per query
@@ -1088,24 +1035,19 @@ extern "C" int tw_decode_attn_mq(const void* q, int64_t sqb, int64_t sqq, const 
   if (B <= 0 || H <= 0) return TW_OK;
   if (dtype != TW_BF16 && dtype != TW_F16 && dtype != TW_F32) return TW_EUNSUPPORTED;
   const int tk_last = Tk + (causal ? Q - 1 : 0);
-  if ((!tk_dev && Tk <= 0) || tk_last > DA_MAX_TK || B * H >= DA_BIG) return TW_EUNSUPPORTED;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
-  if ((sqb | sqq | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
-  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0 || sqq < 0 || soq < 0) return TW_EINVAL;
+  if (B * H >= DA_BIG) return TW_EUNSUPPORTED;
+  DecP p;
+  if (const int st = dec_fill(p, q, sqb, k, ldk, skb, hsk, v, ldv, svb, hsv, o, sob, H, Tk, tk_last, tk_dev, k_start,
+                              scale))
+    return st;
+  if ((sqq & 7) || sqq < 0 || soq < 0) return TW_EINVAL;
   const int QN = Q <= 1 ? 1 : Q <= 2 ? 2 : Q <= 4 ? 4 : 8;
   const int nchunk = (tk_last + DA_SPLIT - 1) / DA_SPLIT;
-  const bool split = !tk_dev && B * H < 640 && nchunk >= 2 && nchunk <= DA_MAX_CHUNK;
+  const bool split = dec_split(tk_dev, B * H, nchunk);
   // one-workgroup path: a query's scores live in DA_MQ_LDS / QN floats of LDS
   if (!split && !tk_dev && tk_last > DA_MQ_LDS / QN) return TW_EUNSUPPORTED;
-  DecP p;
-  p.q = q; p.sqb = sqb;
-  p.k = k; p.ldk = ldk; p.skb = skb;
-  p.v = v; p.ldv = ldv; p.svb = svb;
-  p.o = o; p.sob = sob;
-  p.hsk = hsk; p.hsv = hsv;
-  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.c = scale * 1.4426950408889634f;
   MqP m;
-  m.sqq = sqq; m.soq = soq; m.nq = Q; m.causal = causal ? 1 : 0; m.k_start = k_start;
+  m.sqq = sqq; m.soq = soq; m.nq = Q; m.causal = causal ? 1 : 0;
   switch (QN) {
     case 1: return launch_mq<1>(p, m, B, nchunk, split, dtype, stream);
     case 2: return launch_mq<2>(p, m, B, nchunk, split, dtype, stream);
@@ -1148,14 +1090,10 @@ extern "C" int tw_greedy_select(const void* logits, int64_t ld, int logits_dtype
                                 int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col,
                                 hipStream_t stream) {
   if (B <= 0) return TW_OK;
-  if (V <= 0 || ld < V || !done || !ids || !next_ids) return TW_EINVAL;
-  SelP p;
-  p.logits = logits; p.ld = ld; p.V = V;
-  p.suppress = suppress_bits; p.begin = begin_bits; p.apply_begin = apply_begin;
-  p.eos = eos; p.done = done; p.ids = ids; p.ld_ids = ld_ids; p.col = col; p.next = next_ids;
-  p.t_dev = t_dev; p.begin_col = begin_col;
-  p.ctl = nullptr; p.sum_logp = nullptr; p.vec = sel_vec(logits, ld, V);
-  return launch_select(p, B, logits_dtype, stream);
+  if (sel_bad(ld, V, done, ids, next_ids)) return TW_EINVAL;
+  return launch_select<GreedyK>(sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids,
+                                         col, next_ids, t_dev, begin_col, nullptr, nullptr),
+                                B, V, logits_dtype, stream);
 }
 
 extern "C" int tw_select_sample(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
@@ -1163,13 +1101,9 @@ extern "C" int tw_select_sample(const void* logits, int64_t ld, int logits_dtype
                                 int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col,
                                 const uint32_t* ctl, float* sum_logp, hipStream_t stream) {
   if (B <= 0) return TW_OK;
-  if (V <= 0 || ld < V || !done || !ids || !next_ids) return TW_EINVAL;
+  if (sel_bad(ld, V, done, ids, next_ids)) return TW_EINVAL;
   if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
-  SelP p;
-  p.logits = logits; p.ld = ld; p.V = V;
-  p.suppress = suppress_bits; p.begin = begin_bits; p.apply_begin = apply_begin;
-  p.eos = eos; p.done = done; p.ids = ids; p.ld_ids = ld_ids; p.col = col; p.next = next_ids;
-  p.t_dev = t_dev; p.begin_col = begin_col;
-  p.ctl = ctl; p.sum_logp = sum_logp; p.vec = sel_vec(logits, ld, V);
-  return launch_select(p, B, logits_dtype, stream);
+  return launch_select<GreedyK>(sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids,
+                                         col, next_ids, t_dev, begin_col, ctl, sum_logp),
+                                B, V, logits_dtype, stream);
 }

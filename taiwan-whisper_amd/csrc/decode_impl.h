@@ -18,6 +18,7 @@ struct DecP {
   int64_t hsk, hsv;   // head strides of K and V (64: heads side by side in a row; Tk*64: head-major blocks)
   int H, Tk;
   const int* tk_dev;  // nullable: effective Tk = *tk_dev + Tk (graph-captured decode steps)
+  const int* k_start; // nullable: row b attends keys from k_start[b] (left-padded prompts); null: every row from key 0
   float c;        // scale * log2(e)
 };
 

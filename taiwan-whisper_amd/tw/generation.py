@@ -11,9 +11,11 @@ value is the generated ids only (transformers >= 5 behaviour, the version in thi
 Device layout (one DecodeSession per batch of clips):
   * self-attention cache per decoder layer: bf16 [B][T_max][2d] (k | v); the fused QKV projection
     of a step goes to a [B][3d] staging buffer and tw_kv_append copies k, v to row t; keys /
-    values 0..t are read in place by tw_decode_attn;
-  * cross-attention K/V per decoder layer: bf16 [B*1500][2d], projected once from the encoder
-    output (k has no bias: the zero-bias segment of the fused KV bias);
+    values 0..t are read in place by tw_decode_attn (tw_decode_attn_ks from each row's first real
+    column when the prompts are left-padded; tw_decode_attn_mq for the Q rows of a verify pass);
+  * cross-attention K/V per decoder layer: bf16, head-major (K [B][H][1500][64] then V), projected
+    once from the encoder output (k has no bias: the zero-bias segment of the fused KV bias) and
+    transposed by tw_kv_head_major;
   * logits bf16 [B][Vp]; tw_greedy_select applies the suppress masks, takes the argmax, writes
     the token into the id matrix and the next step's input vector, and tracks finished rows.
 Everything runs on the HIP library.  The step index lives in device memory (t_dev: embedding
@@ -23,14 +25,26 @@ replayed per token; the host reads the finished flags every 8 steps to stop earl
 """
 from __future__ import annotations
 
-import os
 import time
 
 import torch
 
 from . import ops as F
 
-_XKV_HEAD_MAJOR = os.environ.get("TW_XKV_HEAD_MAJOR", "1") != "0"
+
+class _StepBufs:
+    """Activation buffers of M rows on their way through the decoder layers and the head."""
+
+    def __init__(self, model, M):
+        cfg, d, dev, act = model.config, model.config.d_model, model.device, model.act_dtype
+        self.M = M
+        self.x = torch.empty(M, d, dtype=model.stream_dtype, device=dev)
+        self.y = torch.empty(M, d, dtype=act, device=dev)
+        self.qkv = torch.empty(M, 3 * d, dtype=act, device=dev)
+        self.o = torch.empty(M, d, dtype=act, device=dev)
+        self.q = torch.empty(M, d, dtype=act, device=dev)
+        self.h = torch.empty(M, cfg.decoder_ffn_dim, dtype=act, device=dev)
+        self.logits = torch.empty(M, model.Vp, dtype=act, device=dev)
 
 
 class DecodeSession:
@@ -44,7 +58,6 @@ class DecodeSession:
         T_max = T_max + spare
         self.m, self.B, self.Tk, self.T_max = model, B, Tk, T_max
         self.clamp_pos = spare > 0
-        self.mq = None                   # buffers of step_multi (alloc_multi)
         self.d = cfg.d_model
         self.H = self.d // 64
         dev = model.device
@@ -54,27 +67,16 @@ class DecodeSession:
                         for _ in range(cfg.decoder_layers)]
         # cross-attention K/V head-major (K [B][H][Tk][64] then V): each (clip, head) of the per-step
         # cross-attention reads two contiguous runs instead of 128-B rows 2d apart (tw_kv_head_major; the
-        # projection goes through one scratch [B*Tk][2d] block).  TW_XKV_HEAD_MAJOR=0: the projection's own
-        # row-interleaved layout (A/B runs).
-        self.hm = _XKV_HEAD_MAJOR
-        if self.hm:
-            self.cross_kv = [torch.empty(2 * B * self.H * Tk * 64, dtype=act, device=dev)
-                             for _ in range(cfg.decoder_layers)]
-        else:
-            self.cross_kv = [torch.empty(B * Tk, 2 * d, dtype=act, device=dev)
-                             for _ in range(cfg.decoder_layers)]
+        # projection goes through one scratch [B*Tk][2d] block)
+        self.cross_kv = [torch.empty(2 * B * self.H * Tk * 64, dtype=act, device=dev)
+                         for _ in range(cfg.decoder_layers)]
         self.graph = None
         self.xkv_shared = False
         self.set_encoder(enc16)
         self.t_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.cur = torch.zeros(B, dtype=torch.int64, device=dev)       # this step's input ids
-        self.x = torch.empty(B, d, dtype=model.stream_dtype, device=dev)
-        self.y = torch.empty(B, d, dtype=act, device=dev)
-        self.qkv = torch.empty(B, 3 * d, dtype=act, device=dev)
-        self.o = torch.empty(B, d, dtype=act, device=dev)
-        self.q = torch.empty(B, d, dtype=act, device=dev)
-        self.h = torch.empty(B, cfg.decoder_ffn_dim, dtype=act, device=dev)
-        self.logits = torch.empty(B, model.Vp, dtype=act, device=dev)
+        self.buf = _StepBufs(model, B)   # the B rows of step
+        self.mq = None                   # the Q rows of step_multi (alloc_multi)
         # batch <= 8 on the bf16 / fp16 paths: every Linear is one GEMV launch, with the LayerNorm in front of it
         # fused when the residual stream is 16-bit (bit-identical A); larger batches use the skinny GEMM with a
         # separate LayerNorm
@@ -89,39 +91,34 @@ class DecodeSession:
         self.padded = False
         self.shifted = False
 
+    @property
+    def logits(self):
+        """[B][Vp] logits of the last step."""
+        return self.buf.logits
+
     def set_encoder(self, enc16):
         """(Re)project the cross-attention K/V of every decoder layer in place (graph-safe).  enc16 holds B*Tk
-        rows, or Tk rows shared by every row of the batch (the speculative fallback batch of one window: the
-        K/V are projected once and copied, so each row sees exactly the K/V of a batch-1 decode)."""
+        rows, or Tk rows shared by every row of the batch (the speculative fallback batch of one window: each row
+        sees exactly the K/V of a batch-1 decode)."""
         m, d = self.m, self.d
         shared = enc16.shape[0] == self.Tk and self.B > 1
         nb = 1 if shared else self.B
-        # head-major and shared: ONE clip's K/V blocks ([H][Tk][64] K then V, at the front of each layer's buffer),
+        # shared: ONE clip's K/V blocks ([H][Tk][64] K then V, at the front of each layer's buffer),
         # read by every row with batch stride 0 (tw_decode_attn_hs) instead of B copies: the fallback batch's
         # cross-attention reads 1/B of the bytes and each row still sees exactly its batch-1 K/V.  The captured step
         # bakes the call's strides in, so a change of mode drops the graph (recaptured on the next run)
-        xs = self.hm and shared
-        if self.graph is not None and xs != self.xkv_shared:
+        if self.graph is not None and shared != self.xkv_shared:
             self.graph = None
-        self.xkv_shared = xs
-        # head-major: the projection goes through one [B*Tk][2d] scratch block that lives only for this call
+        self.xkv_shared = shared
+        # the projection goes through one [nb*Tk][2d] scratch block that lives only for this call
         # (3.9 GB at the 512-clip large-v2 batch; the caching allocator reuses it for the next window)
-        proj = torch.empty(nb * self.Tk, 2 * d, dtype=m.act_dtype, device=m.device) if self.hm or shared else None
+        proj = torch.empty(nb * self.Tk, 2 * d, dtype=m.act_dtype, device=m.device)
         for i, kv in enumerate(self.cross_kv):
             p = f"model.decoder.layers.{i}.encoder_attn"
             wkv = m.wspan(p + ".k_proj.weight", p + ".v_proj.weight", (2 * d, d))
             bkv = m.wspan(p + ".k_proj.zero_bias", p + ".v_proj.bias", (2 * d,))
-            if self.hm and shared:               # K [H][Tk][64] then V of the one clip, shared by every row
-                m._lin(enc16, wkv, bkv, proj)
-                F.kv_head_major(proj, 2 * d, kv, 1, self.Tk, self.H)
-            elif self.hm:
-                m._lin(enc16, wkv, bkv, proj)
-                F.kv_head_major(proj, 2 * d, kv, nb, self.Tk, self.H)
-            elif shared:
-                m._lin(enc16, wkv, bkv, proj)
-                kv.view(self.B, self.Tk, 2 * d).copy_(proj.view(1, self.Tk, 2 * d).expand(self.B, -1, -1))
-            else:
-                m._lin(enc16, wkv, bkv, kv)
+            m._lin(enc16, wkv, bkv, proj)
+            F.kv_head_major(proj, 2 * d, kv, nb, self.Tk, self.H)
         del proj
 
     def set_pads(self, pads, shift_positions=False):
@@ -147,14 +144,13 @@ class DecodeSession:
             self.k_start.copy_(v)
             self.pos_off.copy_(v)
 
-    def _ln(self, x, name, y=None):
+    def _ln(self, x, name, y):
         m = self.m
-        y = self.y if y is None else y
         F.layernorm_fwd(x, m.ln_param(name + ".weight"), m.ln_param(name + ".bias"), y)
         return y
 
-    def _ln_lin(self, x, ln, w, b, out, flags=F.GEMM_ROUND, kv=None, y=None):
-        """out = Linear(LayerNorm(x)): one GEMV launch (batch <= 4, bf16 stream) or LN + GEMM.  kv: the
+    def _ln_lin(self, x, ln, w, b, out, y, flags=F.GEMM_ROUND, kv=None):
+        """out = Linear(LayerNorm(x)): one GEMV launch (batch <= 4, bf16 stream) or LN (into y) + GEMM.  kv: the
         GEMV also appends columns >= kv[3] to the self-attention cache row (only on the GEMV path)."""
         m = self.m
         if self.gemv_ln:
@@ -181,129 +177,105 @@ class DecodeSession:
             return m.store.v32("model.decoder.embed_tokens.weight"), m.store.v32("model.decoder.embed_positions.weight")
         return m.store.v16("model.decoder.embed_tokens.weight"), m.store.v16("model.decoder.embed_positions.weight")
 
-    def alloc_multi(self, Q):
-        """Activation buffers of step_multi: Q rows each (one row of the batch, Q consecutive positions)."""
-        m, d, dev, act = self.m, self.d, self.m.device, self.m.act_dtype
-        assert self.B == 1 and 1 <= Q <= F.MQ_MAX
-        if self.mq is None or self.mq["Q"] != Q:
-            self.mq = dict(Q=Q, x=torch.empty(Q, d, dtype=m.stream_dtype, device=dev),
-                           y=torch.empty(Q, d, dtype=act, device=dev), qkv=torch.empty(Q, 3 * d, dtype=act, device=dev),
-                           o=torch.empty(Q, d, dtype=act, device=dev), q=torch.empty(Q, d, dtype=act, device=dev),
-                           h=torch.empty(Q, m.config.decoder_ffn_dim, dtype=act, device=dev),
-                           logits=torch.empty(Q, m.Vp, dtype=act, device=dev))
-        return self.mq
-
-    def step_multi(self, Q, ids, select=None):
-        """The forward of ONE row for the Q tokens ids[0..Q) at positions *t_dev .. *t_dev + Q - 1 (the verify pass
-        of assisted decoding): the step's launches with M = Q rows -- the Linears read each weight once for the Q
-        rows (the GEMV at d % 256 == 0 on the 16-bit paths, else the GEMM; a row of either does not depend on M) --
-        K/V of the Q positions to cache rows t .. t+Q-1, self-attention causal among the Q rows and cross-attention
-        through tw_decode_attn_mq (each K / V row loaded once for the Q queries; per query the single-query
-        arithmetic), Q logit rows.  Position-independent (t read on the device); t_dev is NOT advanced: the caller
-        decides how many positions stand (tw_spec_accept).  select(self, logits) runs after the head."""
-        m, d, H, T_max = self.m, self.d, self.H, self.T_max
-        assert self.B == 1 and not self.padded and self.spare_ok(Q)
-        b = self.alloc_multi(Q)
-        x, o, t_dev = b["x"], b["o"], self.t_dev
-        E, Pe = self._embed_tables()
-        F.embed_step_multi(ids, E, Pe, x, t_dev, Q)
-        rows = T_max - (Q - 1)                   # the first of the Q cache rows written is below this
+    def _layers(self, b, sb, rows, self_attn, cross_attn, head=True):
+        """The decoder layers and the head on the b.M rows embedded in b.x: per layer the fused QKV, k and v to the
+        cache (row m of b to cache row *t_dev of the block m * sb elements in; `rows` bounds that row), self_attn(b,
+        cache) into b.o, out-proj, cross-q, cross_attn(b, kv) into b.o, out-proj, MLP.  head=False stops after the
+        last layer."""
+        m, d, t_dev = self.m, self.d, self.t_dev
+        x, o, y = b.x, b.o, b.y
         for i in range(m.config.decoder_layers):
             p = f"model.decoder.layers.{i}"
+            # self attention: fused QKV -> staging; k, v appended to the cache
             wqkv = m.wspan(p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d))
             bqkv = m.wspan(p + ".self_attn.q_proj.bias", p + ".self_attn.v_proj.bias", (3 * d,))
             cache = self.self_kv[i]
-            if self.gemv_ln:        # row j of the GEMV goes to cache row t + j: batch stride = row stride
-                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b["qkv"], kv=(cache, 2 * d, 2 * d, d, t_dev,
-                                                                                     rows), y=b["y"])
+            if self.gemv_ln:        # k, v written to the cache by the QKV GEMV itself
+                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b.qkv, y, kv=(cache, sb, 2 * d, d, t_dev, rows))
             else:
-                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b["qkv"], y=b["y"])
-                F.kv_append(b["qkv"][:, d:], 3 * d, cache, 2 * d, 2 * d, Q, 2 * d, t_dev, rows)
-            F.decode_attn_mq(b["qkv"], Q * 3 * d, 3 * d, cache, 2 * d, 0, cache.view(-1)[d:], 2 * d, 0, o, Q * d, d,
-                             1, H, Q, 1, 0.125, tk_dev=t_dev, tk_max=T_max, causal=True)
+                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b.qkv, y)
+                F.kv_append(b.qkv[:, d:], 3 * d, cache, 2 * d, sb, b.M, 2 * d, t_dev, rows)
+            self_attn(b, cache)
             self._lin(o, m._w16(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x, res=x)
+            # cross attention over the encoder frames
             self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
-                         m._w16(p + ".encoder_attn.q_proj.bias"), b["q"], y=b["y"])
-            kv = self.cross_kv[i]
-            if self.hm:             # the clip's [H][Tk][64] K then V blocks
-                n1 = H * self.Tk * 64
-                F.decode_attn_mq(b["q"], Q * d, d, kv, 64, 0, kv[n1:], 64, 0, o, Q * d, d, 1, H, Q, self.Tk, 0.125,
-                                 hsk=self.Tk * 64, hsv=self.Tk * 64)
-            else:
-                F.decode_attn_mq(b["q"], Q * d, d, kv, 2 * d, 0, kv[:, d:], 2 * d, 0, o, Q * d, d, 1, H, Q, self.Tk,
-                                 0.125)
+                         m._w16(p + ".encoder_attn.q_proj.bias"), b.q, y)
+            cross_attn(b, self.cross_kv[i])
             self._lin(o, m._w16(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"), x,
                       res=x)
-            self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), b["h"],
-                         flags=F.GEMM_ROUND | F.GEMM_GELU, y=b["y"])
-            self._lin(b["h"], m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
-        if self.gemv_ln:
-            self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None,
-                         b["logits"], y=b["y"])
-        else:
-            m.lm_head(self._ln(x, "model.decoder.layer_norm", b["y"]), out=b["logits"])
+            # MLP
+            self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), b.h, y,
+                         flags=F.GEMM_ROUND | F.GEMM_GELU)
+            self._lin(b.h, m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
+        if head and self.gemv_ln:
+            self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None, b.logits, y)
+        elif head:
+            m.lm_head(self._ln(x, "model.decoder.layer_norm", y), out=b.logits)
+
+    def alloc_multi(self, Q):
+        """Activation buffers of step_multi: Q rows each (one row of the batch, Q consecutive positions)."""
+        assert self.B == 1 and 1 <= Q <= F.MQ_MAX
+        if self.mq is None or self.mq.M != Q:
+            self.mq = _StepBufs(self.m, Q)
+        return self.mq
+
+    def _self_attn_mq(self, b, cache):
+        d, Q = self.d, b.M
+        F.decode_attn_mq(b.qkv, Q * 3 * d, 3 * d, cache, 2 * d, 0, cache.view(-1)[d:], 2 * d, 0, b.o, Q * d, d,
+                         1, self.H, Q, 1, 0.125, tk_dev=self.t_dev, tk_max=self.T_max, causal=True)
+
+    def _cross_attn_mq(self, b, kv):        # the clip's [H][Tk][64] K then V blocks
+        d, Q, n1 = self.d, b.M, self.H * self.Tk * 64
+        F.decode_attn_mq(b.q, Q * d, d, kv, 64, 0, kv[n1:], 64, 0, b.o, Q * d, d, 1, self.H, Q, self.Tk, 0.125,
+                         hsk=self.Tk * 64, hsv=self.Tk * 64)
+
+    def step_multi(self, Q, ids, select=None):
+        """The forward of ONE row for the Q tokens ids[0..Q) at positions *t_dev .. *t_dev + Q - 1 (the verify pass
+        of assisted decoding): the step's launches (_layers) with M = Q rows -- the Linears read each weight once for
+        the Q rows (the GEMV at d % 256 == 0 on the 16-bit paths, else the GEMM; a row of either does not depend on M)
+        -- K/V of the Q positions to cache rows t .. t+Q-1 (row j of the buffers to cache row t + j: batch stride =
+        row stride), self-attention causal among the Q rows and cross-attention through tw_decode_attn_mq (each K / V
+        row loaded once for the Q queries; per query the single-query arithmetic), Q logit rows.
+        Position-independent (t read on the device); t_dev is NOT advanced: the caller decides how many positions
+        stand (tw_spec_accept).  select(self, logits) runs after the head."""
+        assert self.B == 1 and not self.padded and self.spare_ok(Q)
+        b = self.alloc_multi(Q)
+        E, Pe = self._embed_tables()
+        F.embed_step_multi(ids, E, Pe, b.x, self.t_dev, Q)
+        # the first of the Q cache rows written is below T_max - (Q - 1)
+        self._layers(b, 2 * self.d, self.T_max - (Q - 1), self._self_attn_mq, self._cross_attn_mq)
         if select is not None:
-            select(self, b["logits"])
+            select(self, b.logits)
 
     def spare_ok(self, Q):
         return self.clamp_pos and Q <= F.MQ_MAX
+
+    def _self_attn(self, b, cache):
+        d, sb = self.d, self.T_max * 2 * self.d
+        F.decode_attn(b.qkv, 3 * d, cache, 2 * d, sb, cache.view(-1)[d:], 2 * d, sb, b.o, d, self.B, self.H, 1, 0.125,
+                      tk_dev=self.t_dev, tk_max=self.T_max, k_start=self.k_start if self.padded else None)
+
+    def _cross_attn(self, b, kv):
+        B, H, Tk, d = self.B, self.H, self.Tk, self.d
+        if self.xkv_shared:     # every row over the one clip's [H][Tk][64] blocks (batch stride 0)
+            F.decode_attn(b.q, d, kv, 64, 0, kv[H * Tk * 64:], 64, 0, b.o, d, B, H, Tk, 0.125, hsk=Tk * 64,
+                          hsv=Tk * 64)
+        else:                   # B*H one-head clips over contiguous [Tk][64] runs
+            F.decode_attn(b.q, 64, kv, 64, Tk * 64, kv[B * H * Tk * 64:], 64, Tk * 64, b.o, 64, B * H, 1, Tk, 0.125)
 
     def step(self, select=None, cur=None, head=True):
         """One decoder step at position *t_dev for input ids `cur` (default: self.cur); then t_dev += 1.
         select = (sup, beg, eos, done, ids, P) runs greedy selection into ids[:, t+1] and cur.  head=False stops
         after the last layer (a step that only fills the caches)."""
-        m, B, d, H, T_max = self.m, self.B, self.d, self.H, self.T_max
+        b, t_dev, T_max = self.buf, self.t_dev, self.T_max
         cur = self.cur if cur is None else cur
         E, Pe = self._embed_tables()
-        x, o, t_dev = self.x, self.o, self.t_dev
-        ks = self.k_start if self.padded else None
         if self.clamp_pos:           # spare rows past the length cap: their positions clamp to the table
-            assert B == 1 and not self.shifted
-            F.embed_step_multi(cur, E, Pe, x, t_dev, 1)
+            assert self.B == 1 and not self.shifted
+            F.embed_step_multi(cur, E, Pe, b.x, t_dev, 1)
         else:
-            F.embed_step(cur, E, Pe, x, t_dev, T_max, pos_off=self.pos_off if self.shifted else None)
-        sb = T_max * 2 * d
-        for i in range(m.config.decoder_layers):
-            p = f"model.decoder.layers.{i}"
-            # self attention: fused QKV -> staging; k, v appended at row t of the cache
-            wqkv = m.wspan(p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d))
-            bqkv = m.wspan(p + ".self_attn.q_proj.bias", p + ".self_attn.v_proj.bias", (3 * d,))
-            cache = self.self_kv[i]
-            if self.gemv_ln:        # k, v of this step written to cache row t by the QKV GEMV itself
-                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, self.qkv, kv=(cache, sb, 2 * d, d, t_dev,
-                                                                                     T_max))
-            else:
-                self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, self.qkv)
-                F.kv_append(self.qkv[:, d:], 3 * d, cache, 2 * d, sb, B, 2 * d, t_dev, T_max)
-            F.decode_attn(self.qkv, 3 * d, cache, 2 * d, sb, cache.view(-1)[d:], 2 * d, sb, o, d, B, H, 1, 0.125,
-                          tk_dev=t_dev, tk_max=T_max, k_start=ks)
-            self._lin(o, m._w16(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x, res=x)
-            # cross attention over the encoder frames
-            self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
-                         m._w16(p + ".encoder_attn.q_proj.bias"), self.q)
-            kv = self.cross_kv[i]
-            if self.xkv_shared:     # every row over the one clip's [H][Tk][64] blocks (batch stride 0)
-                n1 = H * self.Tk * 64
-                F.decode_attn(self.q, d, kv, 64, 0, kv[n1:], 64, 0, o, d, B, H, self.Tk, 0.125, hsk=self.Tk * 64,
-                              hsv=self.Tk * 64)
-            elif self.hm:         # B*H one-head clips over contiguous [Tk][64] runs
-                hv = B * H * self.Tk * 64
-                F.decode_attn(self.q, 64, kv, 64, self.Tk * 64, kv[hv:], 64, self.Tk * 64, o, 64, B * H, 1,
-                              self.Tk, 0.125)
-            else:
-                F.decode_attn(self.q, d, kv, 2 * d, self.Tk * 2 * d, kv[:, d:], 2 * d, self.Tk * 2 * d, o, d, B, H,
-                              self.Tk, 0.125)
-            self._lin(o, m._w16(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"), x,
-                      res=x)
-            # MLP
-            self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), self.h,
-                         flags=F.GEMM_ROUND | F.GEMM_GELU)
-            self._lin(self.h, m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
-        if head and self.gemv_ln:
-            self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None,
-                         self.logits)
-        elif head:
-            m.lm_head(self._ln(x, "model.decoder.layer_norm"), out=self.logits)
+            F.embed_step(cur, E, Pe, b.x, t_dev, T_max, pos_off=self.pos_off if self.shifted else None)
+        self._layers(b, T_max * 2 * self.d, T_max, self._self_attn, self._cross_attn, head)
         if select is not None:
             select(self)
         F.step_advance(t_dev)
@@ -407,7 +379,45 @@ class _Select:
                             col, next_ids, t_dev=t_dev, begin_col=self.P)
 
 
-class _Decoder:
+class _PromptedDecode:
+    """What a plain and an assisted decode of one window share: the session set-up, the prompt prefill with the
+    no-speech probe, and HF's trimming of the result.  Subclasses hold m, B, P, T_max, sel and ns_logp."""
+
+    def _open(self, sess, model, enc, Tk, spare=0):
+        """The session of `model` over this window's encoder rows: built on first use, re-projected in place after."""
+        if sess is None:
+            return DecodeSession(model, enc, self.B, Tk, self.T_max, spare=spare)
+        sess.set_encoder(enc)
+        return sess
+
+    def _probe(self, logits, no_speech):
+        """log-softmax of the raw logits at no_speech's token -> ns_logp (WhisperNoSpeechDetection)."""
+        F.token_logprob(logits, self.m.Vp, self.B, self.m.config.vocab_size, no_speech[1], self.ns_logp)
+
+    def _prefill(self, sessions, no_speech):
+        """Prompt columns 0 .. P - 2 through every session, from position 0; the first session is the one whose
+        logits at the <|startoftranscript|> position the no-speech probe reads."""
+        for sess in sessions:
+            sess.t_dev.zero_()
+        for t in range(self.P - 1):
+            for sess in sessions:
+                sess.cur.copy_(self.sel.ids[:, t])
+                sess.step()
+                if sess is sessions[0] and no_speech is not None and t == no_speech[0]:
+                    self._probe(sess.logits, no_speech)
+
+    def _trim(self, t):
+        """The generated columns up to t without the trailing ones in which every row had already finished (HF stops
+        at the step where the last row emits eos)."""
+        gen = self.sel.ids[:, self.P:t + 1]
+        is_eos = (gen == self.sel.eos).cpu()
+        B = gen.shape[0]
+        first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full((B,), gen.shape[1]))
+        L = int(min(gen.shape[1], int(first.max()) + 1)) if B else 0
+        return gen[:, :L]
+
+
+class _Decoder(_PromptedDecode):
     """One greedy decode of B windows with a fixed prompt; reusable across windows (long-form):
     the captured step graph stays valid because every buffer it touches is reused in place."""
 
@@ -427,20 +437,10 @@ class _Decoder:
         no_speech = (sot_position, token): log-softmax of the raw logits at the <|startoftranscript|>
         position for that token goes to self.ns_logp (WhisperNoSpeechDetection)."""
         sel, P = self.sel, self.P
-        if self.sess is None:
-            self.sess = DecodeSession(self.m, enc16, self.B, self.Tk, self.T_max)
-        else:
-            self.sess.set_encoder(enc16)
-        sess = self.sess
+        sess = self.sess = self._open(self.sess, self.m, enc16, self.Tk)
         sess.set_pads(pads, shift_positions)
         sel.reset(prompt, temperature, seed)
-        sess.t_dev.zero_()
-        V = self.m.config.vocab_size
-        for t in range(P - 1):                                   # prefill the cache with the prompt
-            sess.cur.copy_(sel.ids[:, t])
-            sess.step()
-            if no_speech is not None and t == no_speech[0]:
-                F.token_logprob(sess.logits, self.m.Vp, self.B, V, no_speech[1], self.ns_logp)
+        self._prefill([sess], no_speech)
         sess.cur.copy_(sel.ids[:, P - 1])
         if self.use_graph and sess.graph is None:
             sess.capture(sel)
@@ -451,18 +451,11 @@ class _Decoder:
             else:
                 sess.step(sel)
             if no_speech is not None and t == P - 1 and no_speech[0] == P - 1:
-                F.token_logprob(sess.logits, self.m.Vp, self.B, V, no_speech[1], self.ns_logp)
+                self._probe(sess.logits, no_speech)
             t += 1
             if (t - P) % 8 == 7 and bool(sel.done.all()):
                 break
-        gen = sel.ids[:, P:t + 1]
-        # trim trailing columns in which every row had already finished (HF stops at the step
-        # where the last row emits eos)
-        is_eos = (gen == sel.eos).cpu()
-        B = gen.shape[0]
-        first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full((B,), gen.shape[1]))
-        L = int(min(gen.shape[1], int(first.max()) + 1)) if B else 0
-        return gen[:, :L]
+        return self._trim(t)
 
 
 # Drafted tokens per round when generate(assistant_model=...) is given no num_assistant_tokens.  A guess from byte
@@ -474,7 +467,7 @@ DEFAULT_ASSISTANT_TOKENS = 4
 MAX_ASSISTANT_TOKENS = F.MQ_MAX - 1
 
 
-class _SpecDecoder:
+class _SpecDecoder(_PromptedDecode):
     """Assisted (speculative) greedy decode of ONE window: _Decoder.run's signature and result.  A round: the
     assistant drafts k tokens with its own DecodeSession (k + 1 steps: the last one only puts the last draft's K/V
     into the assistant's cache, without the LM head, so that a fully accepted round leaves the assistant caught up),
@@ -539,13 +532,8 @@ class _SpecDecoder:
             raise NotImplementedError("tw generate: assisted decoding is greedy (temperature 0)")
         sel, sel_a, P, Q = self.sel, self.sel_a, self.P, self.k + 1
         enc_a = enc16 if enc_a is None else enc_a
-        if self.sess is None:
-            self.sess = DecodeSession(self.m, enc16, 1, self.Tk, self.T_max, spare=Q)
-            self.sess_a = DecodeSession(self.a, enc_a, 1, enc_a.shape[0], self.T_max, spare=Q)
-        else:
-            self.sess.set_encoder(enc16)
-            self.sess_a.set_encoder(enc_a)
-        st, sa = self.sess, self.sess_a
+        st = self.sess = self._open(self.sess, self.m, enc16, self.Tk, spare=Q)
+        sa = self.sess_a = self._open(self.sess_a, self.a, enc_a, enc_a.shape[0], spare=Q)
         sel.reset(prompt, 0.0, seed if not isinstance(seed, (list, tuple)) else seed[0])
         sel_a.done.zero_()
         sel_a.last_ts.fill_(-1)
@@ -553,16 +541,7 @@ class _SpecDecoder:
         self.hist.zero_()
         if self.slots is not None:
             self.slots.zero_()
-        st.t_dev.zero_()
-        sa.t_dev.zero_()
-        V = self.m.config.vocab_size
-        for t in range(P - 1):                                   # prefill both caches with the prompt
-            st.cur.copy_(sel.ids[:, t])
-            st.step()
-            if no_speech is not None and t == no_speech[0]:
-                F.token_logprob(st.logits, self.m.Vp, 1, V, no_speech[1], self.ns_logp)
-            sa.cur.copy_(sel.ids[:, t])
-            sa.step()
+        self._prefill([st, sa], no_speech)
         self.vin[:1].copy_(sel.ids[0, P - 1:P])
         if self.use_graph and self.graph is None:
             g = torch.cuda.CUDAGraph()
@@ -576,7 +555,7 @@ class _SpecDecoder:
             else:
                 self._round()
             if r == 0 and no_speech is not None and no_speech[0] == P - 1:
-                F.token_logprob(st.mq["logits"], self.m.Vp, 1, V, no_speech[1], self.ns_logp)
+                self._probe(st.mq.logits, no_speech)
             r += 1
             if r % 4 == 0:
                 t = int(st.t_dev)
@@ -585,10 +564,7 @@ class _SpecDecoder:
         t = int(st.t_dev)
         h = self.hist.tolist()
         self.accepted = h[1:1 + h[0]]
-        gen = sel.ids[:, P:t + 1]
-        is_eos = (gen[0] == sel.eos).cpu()
-        L = min(gen.shape[1], int(is_eos.int().argmax()) + 1) if bool(is_eos.any()) else gen.shape[1]
-        return gen[:, :L]
+        return self._trim(t)
 
 
 class _BeamDecoder:

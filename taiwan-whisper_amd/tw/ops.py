@@ -475,6 +475,32 @@ def gelu_bwd(g, pre, out):
 
 
 # ----------------------------------------------------------------------------- greedy decode (A12)
+MQ_MAX = 8             # query rows per batch row of decode_attn_mq
+MQ_LDS = 12288         # score floats of its one-workgroup path (csrc/decode_impl.h DA_MQ_LDS)
+
+
+def _decode_attn_args(what, q, sqb, sqq, k, ldk, skb, v, ldv, svb, o, sob, soq, B, H, Q, rows, hd, tk_dev, tk_max, hsk,
+                      hsv, k_start):
+    """The checks decode_attn and decode_attn_mq share: dtypes, k_start, tk_dev, and that q / k / v / o hold Q query
+    rows per batch row (sqq / soq apart) and `rows` key rows (None: a call the library refuses, no extents to check).
+    Returns (head strides of K and V, algorithmic bytes: every K and V element of the rows attended once)."""
+    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
+        assert t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16, torch.float32), nm
+    if k_start is not None:
+        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
+        _need(k_start, B, f"{what} k_start")
+    if tk_dev is not None:
+        assert tk_dev.dtype == torch.int32 and tk_max is not None
+    if rows is None:
+        return hd, hd, 0
+    hk, hv = (hd if hsk is None else int(hsk)), (hd if hsv is None else int(hsv))
+    _need(q, (B - 1) * sqb + (Q - 1) * sqq + H * hd, f"{what} q")
+    _need(k, (B - 1) * skb + (rows - 1) * ldk + (H - 1) * hk + hd, f"{what} k")
+    _need(v, (B - 1) * svb + (rows - 1) * ldv + (H - 1) * hv + hd, f"{what} v")
+    _need(o, (B - 1) * sob + (Q - 1) * soq + H * hd, f"{what} o")
+    return hk, hv, 2 * B * rows * H * hd * q.element_size()
+
+
 def decode_attn(q, sqb, k, ldk, skb, v, ldv, svb, o, sob, B, H, Tk, scale, tk_dev=None, tk_max=None, hsk=None,
                 hsv=None, k_start=None):
     """One query row per (b, h) over the first Tk (+ *tk_dev) cached key rows (include/tw_hip.h).
@@ -482,40 +508,24 @@ def decode_attn(q, sqb, k, ldk, skb, v, ldv, svb, o, sob, B, H, Tk, scale, tk_de
     K / V (tw_decode_attn_hs; default 64, heads side by side in a row); skb = svb = 0 shares one clip's K/V.
     k_start: device int32 [B], row b attends keys [k_start[b], Tk) only (tw_decode_attn_ks: left-padded prompts)."""
     hd = 64
-    if k_start is not None:
-        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
-        _need(k_start, B, "decode k_start")
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
-        assert t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16, torch.float32), nm
-    rows = Tk if tk_dev is None else tk_max
-    hk, hv = (hd if hsk is None else int(hsk)), (hd if hsv is None else int(hsv))
-    _need(q, (B - 1) * sqb + H * hd, "decode q")
-    _need(k, (B - 1) * skb + (rows - 1) * ldk + (H - 1) * hk + hd, "decode k")
-    _need(v, (B - 1) * svb + (rows - 1) * ldv + (H - 1) * hv + hd, "decode v")
-    _need(o, (B - 1) * sob + H * hd, "decode o")
-    if tk_dev is not None:
-        assert tk_dev.dtype == torch.int32 and tk_max is not None
-    # algorithmic bytes (KernelTimer family "decode_attn_cross" / "decode_attn_self"): every K and V
-    # element of the rows attended once (self: the host does not know *tk_dev; tk_max bounds it)
-    work = 2 * B * rows * H * hd * q.element_size()
+    # work (KernelTimer family "decode_attn_cross" / "decode_attn_self"): the host does not know *tk_dev of a
+    # self-attention call; tk_max bounds it
+    hk, hv, work = _decode_attn_args("decode", q, sqb, 0, k, ldk, skb, v, ldv, svb, o, sob, 0, B, H, 1,
+                                     Tk if tk_dev is None else tk_max, hd, tk_dev, tk_max, hsk, hsv, k_start)
+    family = "decode_attn_self" if tk_dev is not None else "decode_attn_cross"
     if k_start is not None:
         fn = lambda: call("tw_decode_attn_ks", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb,
                           hv, o.data_ptr(), sob, B, H, Tk, _ptr(tk_dev), k_start.data_ptr(), hd, float(scale), _dt(q),
                           _stream())
-        KernelTimer.wrap("decode_attn_self_ks" if tk_dev is not None else "decode_attn_cross_ks", work, fn)
-        return o
-    if hsk is None and hsv is None:
+        family += "_ks"
+    elif hsk is None and hsv is None:
         fn = lambda: call("tw_decode_attn", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, v.data_ptr(), ldv, svb,
                           o.data_ptr(), sob, B, H, Tk, _ptr(tk_dev), hd, float(scale), _dt(q), _stream())
     else:
         fn = lambda: call("tw_decode_attn_hs", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb,
                           hv, o.data_ptr(), sob, B, H, Tk, _ptr(tk_dev), hd, float(scale), _dt(q), _stream())
-    KernelTimer.wrap("decode_attn_self" if tk_dev is not None else "decode_attn_cross", work, fn)
+    KernelTimer.wrap(family, work, fn)
     return o
-
-
-MQ_MAX = 8             # query rows per batch row of decode_attn_mq
-MQ_LDS = 12288         # score floats of its one-workgroup path (csrc/decode_impl.h DA_MQ_LDS)
 
 
 def decode_attn_mq(q, sqb, sqq, k, ldk, skb, v, ldv, svb, o, sob, soq, B, H, Q, Tk, scale, tk_dev=None, tk_max=None,
@@ -524,24 +534,11 @@ def decode_attn_mq(q, sqb, sqq, k, ldk, skb, v, ldv, svb, o, sob, soq, B, H, Q, 
     q + b*sqb + j*sqq attends keys [k_start[b], Tk (+ *tk_dev) (+ j when causal)); each K / V row is loaded once for
     all Q queries.  tk_max bounds the rows the LAST query may read when Tk comes from the device."""
     hd = int(head_dim)
-    for t, nm in ((q, "q"), (k, "k"), (v, "v"), (o, "o")):
-        assert t.dtype == q.dtype and t.dtype in (torch.bfloat16, torch.float16, torch.float32), nm
-    if k_start is not None:
-        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
-        _need(k_start, B, "decode_mq k_start")
-    if tk_dev is not None:
-        assert tk_dev.dtype == torch.int32 and tk_max is not None
-    if 1 <= Q <= MQ_MAX and hd == 64 and B > 0 and H > 0:      # extents of a call the library will launch
+    rows = None                                                # extents only of a call the library will launch
+    if 1 <= Q <= MQ_MAX and hd == 64 and B > 0 and H > 0:
         rows = Tk + (Q - 1 if causal else 0) if tk_dev is None else tk_max
-        hk, hv = (hd if hsk is None else int(hsk)), (hd if hsv is None else int(hsv))
-        _need(q, (B - 1) * sqb + (Q - 1) * sqq + H * hd, "decode_mq q")
-        _need(k, (B - 1) * skb + (rows - 1) * ldk + (H - 1) * hk + hd, "decode_mq k")
-        _need(v, (B - 1) * svb + (rows - 1) * ldv + (H - 1) * hv + hd, "decode_mq v")
-        _need(o, (B - 1) * sob + (Q - 1) * soq + H * hd, "decode_mq o")
-    else:
-        hk = hv = hd
-        rows = 0
-    work = 2 * B * rows * H * hd * q.element_size()
+    hk, hv, work = _decode_attn_args("decode_mq", q, sqb, sqq, k, ldk, skb, v, ldv, svb, o, sob, soq, B, H, Q, rows, hd,
+                                     tk_dev, tk_max, hsk, hsv, k_start)
     fn = lambda: call("tw_decode_attn_mq", q.data_ptr(), sqb, sqq, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb,
                       hv, o.data_ptr(), sob, soq, B, H, Q, Tk, _ptr(tk_dev), _ptr(k_start), int(bool(causal)), hd,
                       float(scale), _dt(q), _stream())
@@ -601,16 +598,29 @@ def token_bitmask(ids, V, device):
     return words.to(torch.int32).to(device)
 
 
-def greedy_select(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, col, next_ids,
-                  t_dev=None, begin_col=-1):
+def _select_args(what, logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, last_ts=None,
+                 ctl=None, sum_logp=None):
+    """The checks the four selection wrappers share: dtypes and extents of the logits, the id matrix (every column
+    when the column comes from the device), the flags, the masks and, where given, last_ts / ctl / sum_logp."""
     assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
     assert next_ids.dtype == torch.int64 and done.dtype == torch.uint8
-    _need(logits, (B - 1) * ld + V, "greedy logits")
-    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col + 1), "greedy ids")
-    _need(done, B, "greedy done"); _need(next_ids, B, "greedy next")
+    _need(logits, (B - 1) * ld + V, f"{what} logits")
+    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col + 1), f"{what} ids")
+    _need(done, B, f"{what} done"); _need(next_ids, B, f"{what} next")
     for m, nm in ((suppress_bits, "suppress"), (begin_bits, "begin")):
         if m is not None:
-            _need(m, (V + 31) // 32, f"greedy {nm} mask")
+            _need(m, (V + 31) // 32, f"{what} {nm} mask")
+    if last_ts is not None:
+        assert last_ts.dtype == torch.int32
+        _need(last_ts, B, f"{what} last_ts")
+    if ctl is not None:
+        assert ctl.dtype == torch.int32 and ctl.numel() >= 3 * B and sum_logp.dtype == torch.float32
+        _need(sum_logp, B, f"{what} sum_logp")
+
+
+def greedy_select(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, col, next_ids,
+                  t_dev=None, begin_col=-1):
+    _select_args("greedy", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev)
     call("tw_greedy_select", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(apply_begin),
          int(eos), done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev),
          int(begin_col), _stream())
@@ -618,14 +628,8 @@ def greedy_select(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos,
 
 def greedy_select_ts(logits, ld, B, V, suppress_bits, begin_bits, eos, done, ids, col, next_ids, last_ts,
                      begin_col, ts_begin=50364, no_ts=50363, max_initial=-1, t_dev=None):
-    assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
-    assert next_ids.dtype == torch.int64 and done.dtype == torch.uint8 and last_ts.dtype == torch.int32
-    _need(logits, (B - 1) * ld + V, "greedy logits")
-    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col + 1), "greedy ids")
-    _need(done, B, "greedy done"); _need(next_ids, B, "greedy next"); _need(last_ts, B, "greedy last_ts")
-    for m, nm in ((suppress_bits, "suppress"), (begin_bits, "begin")):
-        if m is not None:
-            _need(m, (V + 31) // 32, f"greedy {nm} mask")
+    assert last_ts is not None
+    _select_args("greedy", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, last_ts)
     call("tw_greedy_select_ts", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(eos),
          done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev), int(begin_col),
          int(ts_begin), int(no_ts), int(max_initial if max_initial is not None else -1), last_ts.data_ptr(),
@@ -636,13 +640,9 @@ def select_sample(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos,
                   sum_logp, t_dev=None, begin_col=-1):
     """greedy_select + temperature sampling (ctl: int32[3B], per row bits(1/T), seed lo, hi; 1/T = 0 -> argmax)
     + running log-prob of the chosen token (sum_logp: float32[B])."""
-    assert ctl.dtype == torch.int32 and ctl.numel() >= 3 * B and sum_logp.dtype == torch.float32
-    _need(sum_logp, B, "select sum_logp")
-    assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
-    assert next_ids.dtype == torch.int64 and done.dtype == torch.uint8
-    _need(logits, (B - 1) * ld + V, "select logits")
-    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col + 1), "select ids")
-    _need(done, B, "select done"); _need(next_ids, B, "select next")
+    assert ctl is not None
+    _select_args("select", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, None, ctl,
+                 sum_logp)
     call("tw_select_sample", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(apply_begin),
          int(eos), done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev),
          int(begin_col), ctl.data_ptr(), sum_logp.data_ptr(), _stream())
@@ -650,13 +650,9 @@ def select_sample(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos,
 
 def select_sample_ts(logits, ld, B, V, suppress_bits, begin_bits, eos, done, ids, col, next_ids, last_ts, begin_col,
                      ctl, sum_logp, ts_begin=50364, no_ts=50363, max_initial=-1, t_dev=None):
-    assert ctl.dtype == torch.int32 and ctl.numel() >= 3 * B and sum_logp.dtype == torch.float32
-    _need(sum_logp, B, "select sum_logp")
-    assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
-    assert next_ids.dtype == torch.int64 and done.dtype == torch.uint8 and last_ts.dtype == torch.int32
-    _need(logits, (B - 1) * ld + V, "select logits")
-    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col + 1), "select ids")
-    _need(done, B, "select done"); _need(next_ids, B, "select next"); _need(last_ts, B, "select last_ts")
+    assert last_ts is not None and ctl is not None
+    _select_args("select", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, last_ts, ctl,
+                 sum_logp)
     call("tw_select_sample_ts", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(eos),
          done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev), int(begin_col),
          int(ts_begin), int(no_ts), int(max_initial if max_initial is not None else -1), last_ts.data_ptr(),
