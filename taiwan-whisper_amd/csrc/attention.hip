@@ -15,6 +15,12 @@
 // ds_read_b64_tr_b16 reads of a row-major V tile.  Every LDS tile is [64 rows][64] bf16
 // with 16-B chunk c of row r stored at c ^ (r & 7): conflict-free for both the ds_read_b128
 // row reads and the transposed reads.
+//
+// Structure.  Three kernels (forward, dQ, dK/dV), each instantiated <H, VL> (fp16 words; packed rows).  What they
+// share is written once: attn_frame() (the workgroup's clip, head, rows and base pointers), stage_kv(), causal_nkt(),
+// hidden() (the mask), store4() and zero().  Each kernel keeps its own pipeline.  On the host one attn_fill() builds
+// the AttnP of a dense or packed call, attn_check() decides its status, TW_DISPATCH_HVL picks the instantiation and
+// attn_fwd() / attn_bwd() launch; the eight C entries forward to those.
 #include "common.h"
 
 #include <cstdlib>
@@ -80,6 +86,20 @@ __device__ __forceinline__ bf16x8 pack8e(const f32x4& a, const f32x4& b) {
                 f2e<H>(b[0]), f2e<H>(b[1]), f2e<H>(b[2]), f2e<H>(b[3])};
 }
 
+// four fp32 values rounded to the instantiation's 16-bit type, one 8-byte store
+template <bool H>
+__device__ __forceinline__ void store4(bf16* dst, const f32x4& v) {
+  *(bf16x4*)dst = bf16x4{f2e<H>(v[0]), f2e<H>(v[1]), f2e<H>(v[2]), f2e<H>(v[3])};
+}
+
+template <int N, int M>
+__device__ __forceinline__ void zero(f32x4 (&a)[N][M]) {
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) a[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 struct AttnP {
   const bf16* Q; const bf16* K; const bf16* V; bf16* O; float* lse;
   const bf16* dO; float* Dv; bf16* dQ; bf16* dK; bf16* dV;
@@ -123,6 +143,81 @@ constexpr float NEG_BIG = -1e30f;
 
 __device__ __forceinline__ float fmx(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 
+// One workgroup's place in the problem: its (clip, head), the clip's extents and rows, and its own 128 rows (query
+// rows in the forward and dQ kernels, key rows in dK/dV).
+struct Frame {
+  int lane, wave, g, li;      // g = lane >> 4, li = lane & 15
+  int h;
+  int blk, row;               // first row of the workgroup / of this wave
+  int Tq, Tk;                 // this clip's
+  int off;                    // causal diagonal offset Tk - Tq
+  int64_t qrow0, krow0;       // the clip's first row in the query-side / key-side matrices
+  int64_t lse0;               // lse / Dv index of the clip's query 0
+  const bf16 *Qb, *Kb, *Vb;   // row 0 of the clip, this head's columns
+  // this head's columns of the clip's row r in any query-side (Q, O, dO, dQ) / key-side (K, V, dK, dV) matrix
+  template <class T> __device__ __forceinline__ T* qrow(T* base, int64_t ld, int r = 0) const {
+    return base + (qrow0 + r) * ld + h * 64;
+  }
+  template <class T> __device__ __forceinline__ T* krow(T* base, int64_t ld, int r = 0) const {
+    return base + (krow0 + r) * ld + h * 64;
+  }
+};
+
+// A VL kernel leaves when blk is past its clip's last row (blk >= Tq, or Tk in dK/dV): that test is workgroup-uniform
+// (blk, Tq and Tk depend on the block index only) and must stay ahead of any LDS-DMA or barrier.
+template <bool VL>
+__device__ __forceinline__ Frame attn_frame(const AttnP& p) {
+  Frame f;
+  f.lane = lane_id();
+  f.wave = wave_id_uniform();
+  f.g = f.lane >> 4;
+  f.li = f.lane & 15;
+  int xblk, bh;
+  remap_bh(xblk, bh);
+  const int b = bh / p.H;
+  f.h = bh % p.H;
+  f.blk = xblk * QB;
+  f.row = f.blk + f.wave * QW;
+  f.Tq = p.Tq;
+  f.Tk = p.Tk;
+  clip_rows<VL>(p.offq, b, f.Tq, f.qrow0);
+  clip_rows<VL>(p.offk, b, f.Tk, f.krow0);
+  f.lse0 = VL ? (int64_t)f.h * p.Mq + f.qrow0 : (int64_t)bh * f.Tq;
+  f.Qb = f.qrow(p.Q, p.ldq);
+  f.Kb = f.krow(p.K, p.ldk);
+  f.Vb = f.krow(p.V, p.ldv);
+  f.off = f.Tk - f.Tq;
+  return f;
+}
+
+// K tile kt and V tile kt into stage buf of a [stages][K, V] LDS ring
+__device__ __forceinline__ void stage_kv(const AttnP& p, const Frame& f, char* smem, int buf, int kt) {
+  char* Ks = smem + buf * 2 * TB;
+  const int k0 = kt * KT;
+  stage_tile(f.Kb + (int64_t)k0 * p.ldk, p.ldk, f.Tk - k0, Ks, f.wave, f.lane);
+  stage_tile(f.Vb + (int64_t)k0 * p.ldv, p.ldv, f.Tk - k0, Ks + TB, f.wave, f.lane);
+}
+
+// key tiles a query block walks: all of them, or under the causal mask those its last query can see
+__device__ __forceinline__ int causal_nkt(const AttnP& p, const Frame& f) {
+  int nkt = (f.Tk + KT - 1) / KT;
+  if (p.causal) {
+    const int qmax = min(f.Tq - 1, f.blk + QB - 1);
+    const int kend = qmax + f.off + 1;
+    nkt = min(nkt, (kend + KT - 1) / KT);
+  }
+  return nkt;
+}
+
+// The mask: key `key` is hidden from query q (past the key tail, or above the causal diagonal).  QT: a query past Tq
+// hides every key; the forward leaves that test out (rows past Tq hold zero Q fragments and are never stored).
+// Stated as "hidden", not "visible": in this form all three loops compile to the instructions they were measured
+// with; the other polarity reshapes the forward's masked tiles.
+template <bool QT>
+__device__ __forceinline__ bool hidden(const AttnP& p, const Frame& f, int q, int key) {
+  return (QT ? key >= f.Tk || q >= f.Tq : key >= f.Tk) || (p.causal && key > q + f.off);
+}
+
 // ------------------------------------------------------------------------------------
 // H = false: bf16 Q/K/V/O (autocast); H = true: fp16 (the fp16 decode path: P rounded to fp16 for PV,
 // as SDPA's fp16 flash kernel rounds it)
@@ -135,50 +230,21 @@ template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   constexpr int ST = 3;
   __shared__ __attribute__((aligned(16))) char smem[ST * 2 * TB];   // [ST stages][K, V]
-  const int lane = lane_id(), wave = wave_id_uniform();
-  const int g = lane >> 4, li = lane & 15;
-  int xblk, bh;
-  remap_bh(xblk, bh);
-  const int b = bh / p.H, h = bh % p.H;
-  const int qblk = xblk * QB;
-  const int qw = qblk + wave * QW;
-  int Tq = p.Tq, Tk = p.Tk;
-  int64_t qrow0, krow0;
-  clip_rows<VL>(p.offq, b, Tq, qrow0);
-  clip_rows<VL>(p.offk, b, Tk, krow0);
-  if (VL && qblk >= Tq) return;
-  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
-  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
-  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
-  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
-  const int off = Tk - Tq;   // causal diagonal offset
+  const Frame f = attn_frame<VL>(p);
+  if (VL && f.blk >= f.Tq) return;
+  const int lane = f.lane, g = f.g, li = f.li, qw = f.row, Tq = f.Tq, Tk = f.Tk;
 
   bf16x8 qf[2][2];
 #pragma unroll
   for (int qi = 0; qi < 2; ++qi)
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk) qf[qi][kk] = ld_frag(Qb, p.ldq, qw + qi * 16 + li, Tq, kk, lane);
+    for (int kk = 0; kk < 2; ++kk) qf[qi][kk] = ld_frag(f.Qb, p.ldq, qw + qi * 16 + li, Tq, kk, lane);
 
   f32x4 o[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) o[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero(o);
   float m[2] = {NEG_BIG, NEG_BIG}, l[2] = {0.f, 0.f};
 
-  int nkt = (Tk + KT - 1) / KT;
-  if (p.causal) {
-    const int qmax = min(Tq - 1, qblk + QB - 1);
-    const int kend = qmax + off + 1;
-    nkt = min(nkt, (kend + KT - 1) / KT);
-  }
-
-  auto stage = [&](int buf, int kt) {
-    char* Ks = smem + buf * 2 * TB;
-    const int k0 = kt * KT;
-    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, Tk - k0, Ks, wave, lane);
-    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, Tk - k0, Ks + TB, wave, lane);
-  };
+  const int nkt = causal_nkt(p, f);
   // S^T = K Q^T for one tile, boundary tiles masked (key tail / causal diagonal)
   auto scores = [&](const bf16x8 (&kf)[4][2], f32x4 (&s)[4][2], int k0) {
 #pragma unroll
@@ -187,7 +253,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
       s[kj][0] = mma16<H>(kf[kj][1], qf[0][1], mma16<H>(kf[kj][0], qf[0][0], z));
       s[kj][1] = mma16<H>(kf[kj][1], qf[1][1], mma16<H>(kf[kj][0], qf[1][0], z));
     }
-    const bool need_mask = (k0 + KT > Tk) || (p.causal && k0 + KT - 1 > qw + off);
+    const bool need_mask = (k0 + KT > Tk) || (p.causal && k0 + KT - 1 > qw + f.off);
     if (need_mask) {
 #pragma unroll
       for (int qi = 0; qi < 2; ++qi) {
@@ -196,9 +262,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
         for (int kj = 0; kj < 4; ++kj)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int key = k0 + kj * 16 + 4 * g + r;
-            const bool ok = key < Tk && (!p.causal || key <= q + off);
-            if (!ok) s[kj][qi][r] = -INFINITY;
+            if (hidden<false>(p, f, q, k0 + kj * 16 + 4 * g + r)) s[kj][qi][r] = -INFINITY;
           }
       }
     }
@@ -248,9 +312,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
       ls[qi] = a;
     }
   };
-  stage(0, 0);
+  stage_kv(p, f, smem, 0, 0);
   if (nkt > 1) {
-    stage(1, 1);
+    stage_kv(p, f, smem, 1, 1);
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");      // tile 0 landed (4 DMA per tile per wave), tile 1 flies
   } else {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -273,7 +337,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
     for (int hj = 0; hj < 4; ++hj)
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) vf[hj][ss] = rd_tr(Vs, hj * 16, ss, lane);
-    if (kt + 2 < nkt) stage((kt + 2) % 3, kt + 2);          // the slot tile kt-1 was read from
+    if (kt + 2 < nkt) stage_kv(p, f, smem, (kt + 2) % 3, kt + 2);   // the slot tile kt-1 was read from
     const int k0 = kt * KT;
     f32x4 s[4][2];
     scores(kf, s, k0);
@@ -305,13 +369,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
     const int q = qw + qi * 16 + li;
     if (q < Tq) {
       const float inv = 1.f / lt;
-      bf16* Ob = p.O + (qrow0 + q) * p.ldo + h * 64;
+      bf16* Ob = f.qrow(p.O, p.ldo, q);
 #pragma unroll
-      for (int hj = 0; hj < 4; ++hj) {
-        const f32x4 v = o[hj][qi] * inv;
-        *(bf16x4*)(Ob + hj * 16 + 4 * g) = bf16x4{f2e<H>(v[0]), f2e<H>(v[1]), f2e<H>(v[2]), f2e<H>(v[3])};
-      }
-      if (g == 0 && p.lse) p.lse[lse0 + q] = (m[qi] + log2f(lt)) / LOG2E;
+      for (int hj = 0; hj < 4; ++hj) store4<H>(Ob + hj * 16 + 4 * g, o[hj][qi] * inv);
+      if (g == 0 && p.lse) p.lse[f.lse0 + q] = (m[qi] + log2f(lt)) / LOG2E;
     }
   }
 }
@@ -324,26 +385,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
 template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TB];
-  const int lane = lane_id(), wave = wave_id_uniform();
-  const int g = lane >> 4, li = lane & 15;
-  int xblk, bh;
-  remap_bh(xblk, bh);
-  const int b = bh / p.H, h = bh % p.H;
-  const int qblk = xblk * QB;
-  const int qw = qblk + wave * QW;
-  int Tq = p.Tq, Tk = p.Tk;
-  int64_t qrow0, krow0;
-  clip_rows<VL>(p.offq, b, Tq, qrow0);
-  clip_rows<VL>(p.offk, b, Tk, krow0);
-  if (VL && qblk >= Tq) return;
-  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
-  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
-  const bf16* dOb = p.dO + qrow0 * p.lddo + h * 64;
-  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
-  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
-  const int off = Tk - Tq;
-
-  const bf16* Ob = p.O + qrow0 * p.ldo + h * 64;
+  const Frame f = attn_frame<VL>(p);
+  if (VL && f.blk >= f.Tq) return;
+  const int lane = f.lane, g = f.g, li = f.li, qw = f.row, Tq = f.Tq, Tk = f.Tk;
+  const bf16* dOb = f.qrow(p.dO, p.lddo);
+  const bf16* Ob = f.qrow(p.O, p.ldo);
   bf16x8 qf[2][2], dof[2][2];
   float lse2[2], Dq[2];
 #pragma unroll
@@ -352,39 +398,26 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     float dd = 0.f;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      qf[qi][kk] = ld_frag(Qb, p.ldq, q, Tq, kk, lane);
+      qf[qi][kk] = ld_frag(f.Qb, p.ldq, q, Tq, kk, lane);
       dof[qi][kk] = ld_frag(dOb, p.lddo, q, Tq, kk, lane);
       const bf16x8 of = ld_frag(Ob, p.ldo, q, Tq, kk, lane);
 #pragma unroll
       for (int e = 0; e < 8; ++e) dd += e2f<H>(dof[qi][kk][e]) * e2f<H>(of[e]);
     }
-    lse2[qi] = q < Tq ? p.lse[lse0 + q] * LOG2E : 0.f;
+    lse2[qi] = q < Tq ? p.lse[f.lse0 + q] * LOG2E : 0.f;
     Dq[qi] = swap32_sum(swap16_sum(dd));                 // rows past Tq: zero fragments, D = 0
-    if (g == 0 && q < Tq) p.Dv[lse0 + q] = Dq[qi];
+    if (g == 0 && q < Tq) p.Dv[f.lse0 + q] = Dq[qi];
   }
   f32x4 dq[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) dq[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero(dq);
 
-  int nkt = (Tk + KT - 1) / KT;
-  if (p.causal) {
-    const int qmax = min(Tq - 1, qblk + QB - 1);
-    nkt = min(nkt, (qmax + off + 1 + KT - 1) / KT);
-  }
-  auto stage = [&](int buf, int kt) {
-    char* Ks = smem + buf * 2 * TB;
-    const int k0 = kt * KT;
-    stage_tile(Kb + (int64_t)k0 * p.ldk, p.ldk, Tk - k0, Ks, wave, lane);
-    stage_tile(Vb + (int64_t)k0 * p.ldv, p.ldv, Tk - k0, Ks + TB, wave, lane);
-  };
-  stage(0, 0);
+  const int nkt = causal_nkt(p, f);
+  stage_kv(p, f, smem, 0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   for (int kt = 0; kt < nkt; ++kt) {
     const int cur = kt & 1;
-    if (kt + 1 < nkt) stage(cur ^ 1, kt + 1);
+    if (kt + 1 < nkt) stage_kv(p, f, smem, cur ^ 1, kt + 1);
     const char* Ks = smem + cur * 2 * TB;
     const char* Vs = Ks + TB;
     f32x4 s[4][2], dp[4][2];
@@ -404,7 +437,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
     const int k0 = kt * KT;
     // P recomputed with the forward's exp2 (v_exp_f32) and, on interior tiles (no key tail, no query tail, not on
     // the causal diagonal: wave-uniform), without the per-element mask
-    const bool need_mask = (k0 + KT > Tk) || (qw + QW > Tq) || (p.causal && k0 + KT - 1 > qw + off);
+    const bool need_mask = (k0 + KT > Tk) || (qw + QW > Tq) || (p.causal && k0 + KT - 1 > qw + f.off);
 #pragma unroll
     for (int qi = 0; qi < 2; ++qi) {
       const int q = qw + qi * 16 + li;
@@ -412,8 +445,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
       for (int kj = 0; kj < 4; ++kj)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int key = k0 + kj * 16 + 4 * g + r;
-          const bool ok = !need_mask || (key < Tk && q < Tq && (!p.causal || key <= q + off));
+          const bool ok = !need_mask || !hidden<true>(p, f, q, k0 + kj * 16 + 4 * g + r);
           // masked scores as exp2(-inf) = 0: a select, not a branch per element (interior tiles: ok is always true)
           const float pr = __builtin_amdgcn_exp2f(ok ? s[kj][qi][r] * p.scale_log2 - lse2[qi] : -INFINITY);
           s[kj][qi][r] = pr * (dp[kj][qi][r] - Dq[qi]);   // dS^T
@@ -438,12 +470,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
   for (int qi = 0; qi < 2; ++qi) {
     const int q = qw + qi * 16 + li;
     if (q < Tq) {
-      bf16* out = p.dQ + (qrow0 + q) * p.lddq + h * 64;
+      bf16* out = f.qrow(p.dQ, p.lddq, q);
 #pragma unroll
-      for (int hj = 0; hj < 4; ++hj) {
-        const f32x4 v = dq[hj][qi] * p.scale;
-        *(bf16x4*)(out + hj * 16 + 4 * g) = bf16x4{f2e<H>(v[0]), f2e<H>(v[1]), f2e<H>(v[2]), f2e<H>(v[3])};
-      }
+      for (int hj = 0; hj < 4; ++hj) store4<H>(out + hj * 16 + 4 * g, dq[hj][qi] * p.scale);
     }
   }
 }
@@ -455,24 +484,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnP p) {
 template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TB + 2 * 2 * 64 * 4];
-  const int lane = lane_id(), wave = wave_id_uniform();
-  const int g = lane >> 4, li = lane & 15;
-  int xblk, bh;
-  remap_bh(xblk, bh);
-  const int b = bh / p.H, h = bh % p.H;
-  const int kblk = xblk * QB;
-  const int kw = kblk + wave * QW;
-  int Tq = p.Tq, Tk = p.Tk;
-  int64_t qrow0, krow0;
-  clip_rows<VL>(p.offq, b, Tq, qrow0);
-  clip_rows<VL>(p.offk, b, Tk, krow0);
-  if (VL && kblk >= Tk) return;     // a clip without queries still writes its (zero) dK / dV rows below
-  const int64_t lse0 = VL ? (int64_t)h * p.Mq + qrow0 : (int64_t)bh * Tq;
-  const bf16* Qb = p.Q + qrow0 * p.ldq + h * 64;
-  const bf16* dOb = p.dO + qrow0 * p.lddo + h * 64;
-  const bf16* Kb = p.K + krow0 * p.ldk + h * 64;
-  const bf16* Vb = p.V + krow0 * p.ldv + h * 64;
-  const int off = Tk - Tq;
+  const Frame f = attn_frame<VL>(p);   // blk, row: this workgroup's / wave's first key
+  if (VL && f.blk >= f.Tk) return;     // a clip without queries still writes its (zero) dK / dV rows below
+  const int lane = f.lane, g = f.g, li = f.li, kw = f.row, Tq = f.Tq, Tk = f.Tk;
+  const bf16* dOb = f.qrow(p.dO, p.lddo);
   float* rowc = (float*)(smem + 4 * TB);   // [2 stages][lse2 64 | D 64]
 
   bf16x8 kf[2][2], vf[2][2];
@@ -480,30 +495,28 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   for (int kj = 0; kj < 2; ++kj)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      kf[kj][kk] = ld_frag(Kb, p.ldk, kw + kj * 16 + li, Tk, kk, lane);
-      vf[kj][kk] = ld_frag(Vb, p.ldv, kw + kj * 16 + li, Tk, kk, lane);
+      kf[kj][kk] = ld_frag(f.Kb, p.ldk, kw + kj * 16 + li, Tk, kk, lane);
+      vf[kj][kk] = ld_frag(f.Vb, p.ldv, kw + kj * 16 + li, Tk, kk, lane);
     }
   f32x4 dk[4][2], dv[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) dk[i][j] = dv[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero(dk);
+  zero(dv);
 
   const int nqt_all = (Tq + KT - 1) / KT;
   int qt0 = 0;
   if (p.causal) {
-    const int qmin = kblk - off;   // first query that can see this key block
+    const int qmin = f.blk - f.off;   // first query that can see this key block
     qt0 = qmin > 0 ? qmin / KT : 0;
   }
   auto stage = [&](int buf, int qt) {
     char* Qs = smem + buf * 2 * TB;
     const int q0 = qt * KT;
-    stage_tile(Qb + (int64_t)q0 * p.ldq, p.ldq, Tq - q0, Qs, wave, lane);
-    stage_tile(dOb + (int64_t)q0 * p.lddo, p.lddo, Tq - q0, Qs + TB, wave, lane);
+    stage_tile(f.Qb + (int64_t)q0 * p.ldq, p.ldq, Tq - q0, Qs, f.wave, lane);
+    stage_tile(dOb + (int64_t)q0 * p.lddo, p.lddo, Tq - q0, Qs + TB, f.wave, lane);
     if (threadIdx.x < 64) {
       const int q = q0 + threadIdx.x;
-      rowc[buf * 128 + threadIdx.x] = q < Tq ? p.lse[lse0 + q] * LOG2E : 0.f;
-      rowc[buf * 128 + 64 + threadIdx.x] = q < Tq ? p.Dv[lse0 + q] : 0.f;
+      rowc[buf * 128 + threadIdx.x] = q < Tq ? p.lse[f.lse0 + q] * LOG2E : 0.f;
+      rowc[buf * 128 + 64 + threadIdx.x] = q < Tq ? p.Dv[f.lse0 + q] : 0.f;
     }
   };
   if (qt0 < nqt_all) {
@@ -534,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
       }
     }
     // interior tiles (no query tail, no key tail, not on the causal diagonal: wave-uniform) skip the mask
-    const bool need_mask = (q0 + KT > Tq) || (kw + QW > Tk) || (p.causal && kw + QW - 1 > q0 + off);
+    const bool need_mask = (q0 + KT > Tq) || (kw + QW > Tk) || (p.causal && kw + QW - 1 > q0 + f.off);
 #pragma unroll
     for (int qf = 0; qf < 4; ++qf)
 #pragma unroll
@@ -544,8 +557,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
         const float l2 = lrow[ql], Dq = lrow[64 + ql];
 #pragma unroll
         for (int kj = 0; kj < 2; ++kj) {
-          const int key = kw + kj * 16 + li;
-          const bool ok = !need_mask || (q < Tq && key < Tk && (!p.causal || key <= q + off));
+          const bool ok = !need_mask || !hidden<true>(p, f, q, kw + kj * 16 + li);
           const float pr = __builtin_amdgcn_exp2f(ok ? s[qf][kj][r] * p.scale_log2 - l2 : -INFINITY);   // select, no branch
           s[qf][kj][r] = pr;                              // P
           dp[qf][kj][r] = pr * (dp[qf][kj][r] - Dq);      // dS
@@ -575,23 +587,103 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(AttnP p) {
   for (int kj = 0; kj < 2; ++kj) {
     const int key = kw + kj * 16 + li;
     if (key < Tk) {
-      bf16* ok_ = p.dK + (krow0 + key) * p.lddk + h * 64;
-      bf16* ov_ = p.dV + (krow0 + key) * p.lddv + h * 64;
+      bf16* ok_ = f.krow(p.dK, p.lddk, key);
+      bf16* ov_ = f.krow(p.dV, p.lddv, key);
 #pragma unroll
       for (int hj = 0; hj < 4; ++hj) {
-        const f32x4 a = dk[hj][kj] * p.scale;
-        const f32x4 c = dv[hj][kj];
-        *(bf16x4*)(ok_ + hj * 16 + 4 * g) = bf16x4{f2e<H>(a[0]), f2e<H>(a[1]), f2e<H>(a[2]), f2e<H>(a[3])};
-        *(bf16x4*)(ov_ + hj * 16 + 4 * g) = bf16x4{f2e<H>(c[0]), f2e<H>(c[1]), f2e<H>(c[2]), f2e<H>(c[3])};
+        store4<H>(ok_ + hj * 16 + 4 * g, dk[hj][kj] * p.scale);
+        store4<H>(ov_ + hj * 16 + 4 * g, dv[hj][kj]);
       }
     }
   }
 }
 
-bool check_common(const void* Q, const void* K, const void* V, int64_t ldq, int64_t ldk, int64_t ldv) {
-  if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)V) & 15) return false;
-  if ((ldq | ldk | ldv) & 7) return false;
-  return true;
+// ------------------------------------------------------------------------------------
+// Host side.  Dense entries: B clips of Tq x Tk, lse (and the backward's workspace, the D = rowsum(dO*O) vector)
+// [B][H][Tq].
+// Packed rows (the trainer's decoder: clip b holds only its first n_b rows, the clips concatenated).  offq: B + 1
+// cumulative query-row offsets (device, int32), Mq = offq[B], max_q = the longest clip.  offk: the same for the
+// keys (causal self-attention passes one array for both), or null for dense keys at b*Tk (cross-attention against
+// the encoder's 1500 rows); Tk is the dense key count, or with offk the longest clip's.  lse (and the backward's
+// workspace) are [H][Mq].  The per-clip tile order is the dense kernels', so every clip's rows equal a dense call
+// on that clip alone bit for bit.  A clip without queries gets zero dK / dV rows.
+
+// The AttnP of any entry: a dense call passes offq = offk = null, Mq = 0; a packed one its max_q as Tq.  The forward
+// leaves the backward's tensors out.
+AttnP attn_fill(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const void* O,
+                int64_t ldo, const float* lse, int B, int H, int Tq, int Tk, int causal, float scale, const int* offq,
+                const int* offk, int Mq, const void* dO = nullptr, int64_t lddo = 0, void* dQ = nullptr,
+                int64_t lddq = 0, void* dK = nullptr, int64_t lddk = 0, void* dV = nullptr, int64_t lddv = 0,
+                float* workspace = nullptr) {
+  AttnP p = {};
+  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O; p.lse = (float*)lse;
+  p.dO = (const bf16*)dO; p.Dv = workspace; p.dQ = (bf16*)dQ; p.dK = (bf16*)dK; p.dV = (bf16*)dV;
+  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
+  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
+  p.scale = scale; p.scale_log2 = scale * LOG2E;
+  p.offq = offq; p.offk = offk; p.Mq = Mq;
+  return p;
+}
+
+constexpr int ATTN_LAUNCH = -1;
+
+// The status of a call that launches nothing, else ATTN_LAUNCH.  packed: a tw_attn_*_varlen entry (p.Tq is its
+// max_q); bwd: the backward pass, whose dQ kernel reads O and dO in 16-byte fragments (the forward stores O in 8-byte
+// pieces).  The order of the tests is part of the C ABI's behaviour.
+int attn_check(const AttnP& p, int head_dim, bool packed, bool bwd) {
+  if (head_dim != 64) return TW_EUNSUPPORTED;
+  // scale > 0 (the forward takes the row max on raw scores), NaN failing too: tested on the bits (0 < bits <= +inf),
+  // because this file is built with -fno-honor-nans, which lets the compiler turn !(scale > 0.f) into scale <= 0.f
+  if (__builtin_bit_cast(uint32_t, p.scale) - 1u >= 0x7f800000u) return TW_EINVAL;
+  if (packed) {
+    if (!(p.offq != nullptr && p.B > 0 && p.Mq >= 0 && p.Tq >= 0 && p.Tq <= p.Mq && p.Tk >= 0 &&
+          !(p.causal && p.Tq > p.Tk)))
+      return TW_EINVAL;
+    // without queries the backward still has dK / dV to zero (dense keys)
+    if (p.Tk == 0 || (!bwd && (p.Mq == 0 || p.Tq == 0))) return TW_OK;
+  } else if (p.B <= 0 || p.Tq <= 0 || p.Tk <= 0) {
+    return TW_OK;
+  }
+  if ((((uintptr_t)p.Q | (uintptr_t)p.K | (uintptr_t)p.V) & 15) || ((p.ldq | p.ldk | p.ldv) & 7)) return TW_EINVAL;
+  if (bwd ? (((uintptr_t)p.dO | (uintptr_t)p.O) & 15) || ((p.lddo | p.ldo) & 7) : (p.ldo & 3) != 0) return TW_EINVAL;
+  if (!packed && p.causal && p.Tq > p.Tk) return TW_EINVAL;
+  return ATTN_LAUNCH;
+}
+
+// run the statement with H (fp16 words, else bf16) and VL (packed rows) as constants:
+// TW_DISPATCH_HVL(half, packed, hipLaunchKernelGGL((K<H, VL>), ...))
+#define TW_DISPATCH_HVL(half, packed, ...)                                      \
+  do {                                                                          \
+    if ((half) && (packed)) { constexpr bool H = true, VL = true; __VA_ARGS__; } \
+    else if (half) { constexpr bool H = true, VL = false; __VA_ARGS__; }        \
+    else if (packed) { constexpr bool H = false, VL = true; __VA_ARGS__; }      \
+    else { constexpr bool H = false, VL = false; __VA_ARGS__; }                 \
+  } while (0)
+
+dim3 attn_grid(const AttnP& p, int rows) { return dim3((rows + QB - 1) / QB, p.B * p.H); }
+
+// half: fp16 Q/K/V/O (HF Whisper with torch_dtype=float16: SDPA over fp16 projections, run_eval.py:99,500-509)
+int attn_fwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream) {
+  if (const int st = attn_check(p, head_dim, packed, false); st != ATTN_LAUNCH) return st;
+  TW_DISPATCH_HVL(half, packed,
+                  hipLaunchKernelGGL((attn_fwd_kernel<H, VL>), attn_grid(p, p.Tq), dim3(256), 0, stream, p));
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+// half: fp16 Q/K/V/O/dO/dQ/dK/dV (the student's SDPA backward under fp16 autocast, run_distillation.py:815-817
+// mixed_precision="fp16"): the bf16 kernels instantiated for fp16 words (P and dS rounded to fp16 for their MFMAs)
+int attn_bwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream) {
+  if (const int st = attn_check(p, head_dim, packed, true); st != ATTN_LAUNCH) return st;
+  // dQ (and D, which the dK/dV kernel reads) first, then dK/dV; with packed queries and dense keys the dK/dV launch
+  // runs even when no clip has a query (zeros)
+  TW_DISPATCH_HVL(half, packed, {
+    if (p.Tq > 0)
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<H, VL>), attn_grid(p, p.Tq), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<H, VL>), attn_grid(p, p.Tk), dim3(256), 0, stream, p);
+  });
+  TW_CHECK_LAUNCH();
+  return TW_OK;
 }
 
 }  // namespace
@@ -599,169 +691,49 @@ bool check_common(const void* Q, const void* K, const void* V, int64_t ldq, int6
 extern "C" int tw_attn_fwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
                            int64_t ldo, float* lse, int B, int H, int Tq, int Tk, int head_dim, int causal, float scale,
                            hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
-  if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
-  if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
-  if (causal && Tq > Tk) return TW_EINVAL;
-  AttnP p = {};
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O; p.lse = lse;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
-  p.scale = scale; p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL((attn_fwd_kernel<false, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Tq, Tk, causal, scale, nullptr, nullptr, 0),
+                  head_dim, false, false, stream);
 }
 
-// fp16 Q/K/V/O (HF Whisper with torch_dtype=float16: SDPA over fp16 projections, run_eval.py:99,500-509)
 extern "C" int tw_attn_fwd_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                                void* O, int64_t ldo, float* lse, int B, int H, int Tq, int Tk, int head_dim, int causal,
                                float scale, hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
-  if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
-  if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
-  if (causal && Tq > Tk) return TW_EINVAL;
-  AttnP p = {};
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O; p.lse = lse;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
-  p.scale = scale; p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL((attn_fwd_kernel<true, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Tq, Tk, causal, scale, nullptr, nullptr, 0),
+                  head_dim, false, true, stream);
 }
-
-namespace {
-// workspace: B*H*Tq floats (the D = rowsum(dO*O) vector); half: fp16 words (fp16-autocast training), else bf16
-int attn_bwd_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, const void* O,
-                 int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ, int64_t lddq, void* dK,
-                 int64_t lddk, void* dV, int64_t lddv, int B, int H, int Tq, int Tk, int head_dim, int causal,
-                 float scale, float* workspace, bool half, hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
-  if (B <= 0 || Tq <= 0 || Tk <= 0) return TW_OK;
-  if (!check_common(Q, K, V, ldq, ldk, ldv) || ((uintptr_t)dO & 15) || (lddo & 7) || ((uintptr_t)O & 15) || (ldo & 7))
-    return TW_EINVAL;
-  if (causal && Tq > Tk) return TW_EINVAL;
-  AttnP p = {};
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.lse = (float*)lse; p.O = (bf16*)O;
-  p.dO = (const bf16*)dO; p.Dv = workspace; p.dQ = (bf16*)dQ; p.dK = (bf16*)dK; p.dV = (bf16*)dV;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-  p.B = B; p.H = H; p.Tq = Tq; p.Tk = Tk; p.causal = causal;
-  p.scale = scale; p.scale_log2 = scale * LOG2E;
-  // dQ (and D, which the dK/dV kernel reads) first, then dK/dV
-  if (half) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, false>), dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, false>), dim3((Tq + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, false>), dim3((Tk + QB - 1) / QB, B * H), dim3(256), 0, stream, p);
-  }
-  TW_CHECK_LAUNCH();
-  return TW_OK;
-}
-}  // namespace
 
 extern "C" int tw_attn_bwd(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                            const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
                            int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int H, int Tq, int Tk,
                            int head_dim, int causal, float scale, float* workspace, hipStream_t stream) {
-  return attn_bwd_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, B, H, Tq, Tk,
-                      head_dim, causal, scale, workspace, false, stream);
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Tq, Tk, causal, scale, nullptr, nullptr, 0, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, false, false, stream);
 }
 
-// fp16 Q/K/V/O/dO/dQ/dK/dV (the student's SDPA backward under fp16 autocast, run_distillation.py:815-817
-// mixed_precision="fp16"): the bf16 kernels instantiated for fp16 words (P and dS rounded to fp16 for their MFMAs)
 extern "C" int tw_attn_bwd_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                                const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
                                int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, int B, int H, int Tq,
                                int Tk, int head_dim, int causal, float scale, float* workspace, hipStream_t stream) {
-  return attn_bwd_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, B, H, Tq, Tk,
-                      head_dim, causal, scale, workspace, true, stream);
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, Tq, Tk, causal, scale, nullptr, nullptr, 0, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, false, true, stream);
 }
-
-// ------------------------------------------------------------------------------------
-// Packed rows (the trainer's decoder: clip b holds only its first n_b rows, the clips concatenated).  offq: B + 1
-// cumulative query-row offsets (device, int32), Mq = offq[B], max_q = the longest clip.  offk: the same for the
-// keys (causal self-attention passes one array for both), or null for dense keys at b*Tk (cross-attention against
-// the encoder's 1500 rows); Tk is the dense key count, or with offk the longest clip's.  lse (and the backward's
-// workspace) are [H][Mq].  The per-clip tile order is the dense kernels', so every clip's rows equal a dense call
-// on that clip alone bit for bit.  A clip without queries gets zero dK / dV rows.
-namespace {
-bool varlen_args_ok(const int* offq, int B, int Mq, int max_q, int Tk, int causal) {
-  return offq != nullptr && B > 0 && Mq >= 0 && max_q >= 0 && max_q <= Mq && Tk >= 0 && !(causal && max_q > Tk);
-}
-
-int attn_fwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
-                        int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
-                        int Tk, int head_dim, int causal, float scale, bool half, hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
-  if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
-  if (Mq == 0 || max_q == 0 || Tk == 0) return TW_OK;
-  if (!check_common(Q, K, V, ldq, ldk, ldv) || (ldo & 3)) return TW_EINVAL;
-  AttnP p = {};
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.O = (bf16*)O; p.lse = lse;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
-  p.B = B; p.H = H; p.Tq = max_q; p.Tk = Tk; p.causal = causal;
-  p.scale = scale; p.scale_log2 = scale * LOG2E;
-  p.offq = offq; p.offk = offk; p.Mq = Mq;
-  const dim3 grid((max_q + QB - 1) / QB, B * H);
-  if (half) hipLaunchKernelGGL((attn_fwd_kernel<true, true>), grid, dim3(256), 0, stream, p);
-  else hipLaunchKernelGGL((attn_fwd_kernel<false, true>), grid, dim3(256), 0, stream, p);
-  TW_CHECK_LAUNCH();
-  return TW_OK;
-}
-
-// workspace: H*Mq floats
-int attn_bwd_varlen_run(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
-                        const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
-                        int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq, const int* offk,
-                        int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
-                        float* workspace, bool half, hipStream_t stream) {
-  if (head_dim != 64) return TW_EUNSUPPORTED;
-  if (!(scale > 0.f)) return TW_EINVAL;   // the forward takes the row max on raw scores; NaN fails too
-  if (!varlen_args_ok(offq, B, Mq, max_q, Tk, causal)) return TW_EINVAL;
-  if (Tk == 0) return TW_OK;
-  if (!check_common(Q, K, V, ldq, ldk, ldv) || ((uintptr_t)dO & 15) || (lddo & 7) || ((uintptr_t)O & 15) || (ldo & 7))
-    return TW_EINVAL;
-  AttnP p = {};
-  p.Q = (const bf16*)Q; p.K = (const bf16*)K; p.V = (const bf16*)V; p.lse = (float*)lse; p.O = (bf16*)O;
-  p.dO = (const bf16*)dO; p.Dv = workspace; p.dQ = (bf16*)dQ; p.dK = (bf16*)dK; p.dV = (bf16*)dV;
-  p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo; p.lddo = lddo; p.lddq = lddq; p.lddk = lddk; p.lddv = lddv;
-  p.B = B; p.H = H; p.Tq = max_q; p.Tk = Tk; p.causal = causal;
-  p.scale = scale; p.scale_log2 = scale * LOG2E;
-  p.offq = offq; p.offk = offk; p.Mq = Mq;
-  const dim3 gq((max_q + QB - 1) / QB, B * H), gk((Tk + QB - 1) / QB, B * H);
-  // dQ (and D) first, then dK/dV; with dense keys the dK/dV launch runs even when no clip has a query (zeros)
-  if (half) {
-    if (max_q > 0) hipLaunchKernelGGL((attn_bwd_dq_kernel<true, true>), gq, dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<true, true>), gk, dim3(256), 0, stream, p);
-  } else {
-    if (max_q > 0) hipLaunchKernelGGL((attn_bwd_dq_kernel<false, true>), gq, dim3(256), 0, stream, p);
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<false, true>), gk, dim3(256), 0, stream, p);
-  }
-  TW_CHECK_LAUNCH();
-  return TW_OK;
-}
-}  // namespace
 
 extern "C" int tw_attn_fwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
                                   void* O, int64_t ldo, float* lse, const int* offq, const int* offk, int B, int H,
                                   int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
                                   hipStream_t stream) {
-  return attn_fwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, head_dim, causal,
-                             scale, false, stream);
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq),
+                  head_dim, true, false, stream);
 }
 
 extern "C" int tw_attn_fwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
                                       int64_t ldv, void* O, int64_t ldo, float* lse, const int* offq, const int* offk,
                                       int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
                                       hipStream_t stream) {
-  return attn_fwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, head_dim, causal,
-                             scale, true, stream);
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq),
+                  head_dim, true, true, stream);
 }
 
 extern "C" int tw_attn_bwd_varlen(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
@@ -769,8 +741,9 @@ extern "C" int tw_attn_bwd_varlen(const void* Q, int64_t ldq, const void* K, int
                                   int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
                                   const int* offk, int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
                                   float scale, float* workspace, hipStream_t stream) {
-  return attn_bwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, offq, offk, B,
-                             H, Mq, max_q, Tk, head_dim, causal, scale, workspace, false, stream);
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, true, false, stream);
 }
 
 extern "C" int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
@@ -779,6 +752,7 @@ extern "C" int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K,
                                       int64_t lddv, const int* offq, const int* offk, int B, int H, int Mq, int max_q,
                                       int Tk, int head_dim, int causal, float scale, float* workspace,
                                       hipStream_t stream) {
-  return attn_bwd_varlen_run(Q, ldq, K, ldk, V, ldv, O, ldo, dO, lddo, lse, dQ, lddq, dK, lddk, dV, lddv, offq, offk, B,
-                             H, Mq, max_q, Tk, head_dim, causal, scale, workspace, true, stream);
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, true, true, stream);
 }

@@ -48,7 +48,9 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         t = e0.elapsed_time(e1) / 3
-        print(f"bwd {name:9s} {t*1e3:8.1f}us {2.5*fl/t/1e9:7.1f} TF/s", flush=True)
+        bits = lambda x: int(x.contiguous().view(torch.int16).to(torch.int64).sum())
+        print(f"bwd {name:9s} {t*1e3:8.1f}us {2.5*fl/t/1e9:7.1f} TF/s  bits dq {bits(dq)} dk {bits(dkv[:, :d])} "
+              f"dv {bits(dkv[:, d:])}", flush=True)
 
 
 if __name__ == "__main__":

@@ -553,11 +553,27 @@ class WhisperForConditionalGeneration:
         self._lin(h, w, b, out, res=x, flags=flags)
         return out, None
 
+    def _attn_fwd(self, x, p, q, ldq, k, v, ldkv, B, T, Tk, causal, tape, pk):
+        """What the self- and cross-attention blocks share: o = attention of B clips of T queries over Tk keys (Tk None:
+        self-attention, the keys are the queries' rows; pk: packed queries and, for self-attention, packed keys), then
+        out_proj onto the stream x -> (_res_out's result, o, lse); lse only with a tape."""
+        d = self.config.d_model
+        H = d // 64
+        M = B * T if pk is None else pk.M
+        o = self._rows(M, d, self.act_dtype)
+        lse = torch.empty(H * M, dtype=torch.float32, device=self.device) if tape is not None else None
+        if pk is None:
+            F.attn_fwd(q, ldq, k, ldkv, v, ldkv, o, d, lse, B, H, T, T if Tk is None else Tk, causal, 0.125)
+        else:       # packed queries; cross-attention runs them against each clip's dense Tk encoder rows
+            offk, Tk = (pk.off, pk.max_len) if Tk is None else (None, Tk)
+            F.attn_fwd_varlen(q, ldq, k, ldkv, v, ldkv, o, d, lse, pk.off, offk, pk.B, H, M, pk.max_len, Tk, causal, 0.125)
+        out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
+        return out, o, lse
+
     def _attn_block(self, x, p, B, T, causal, tape=None, pend=None, pk=None):
         """x: residual stream [B*T, d] (+ a pending update) -> (new stream, pending update) (self attention).
         pk: packed rows (PackedRows) -- x holds pk.M rows and the attention runs per clip over its own rows."""
-        cfg, d = self.config, self.config.d_model
-        H = d // 64
+        d = self.config.d_model
         sv = {} if tape is not None else None
         x, y = self._ln_in(x, pend, p + "_layer_norm", sv)
         M = B * T if pk is None else pk.M
@@ -565,21 +581,13 @@ class WhisperForConditionalGeneration:
         wqkv = self.wspan(p + ".q_proj.weight", p + ".v_proj.weight", (3 * d, d))
         bqkv = self.wspan(p + ".q_proj.bias", p + ".v_proj.bias", (3 * d,))
         self._lin(y, wqkv, bqkv, qkv)
-        o = self._rows(M, d, self.act_dtype)
-        lse = torch.empty(H * M, dtype=torch.float32, device=self.device) if tape is not None else None
-        if pk is None:
-            F.attn_fwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, o, d, lse, B, H, T, T, causal, 0.125)
-        else:
-            F.attn_fwd_varlen(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, o, d, lse, pk.off, pk.off, pk.B, H,
-                              M, pk.max_len, pk.max_len, causal, 0.125)
-        out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
+        out, o, lse = self._attn_fwd(x, p, qkv, 3 * d, qkv[:, d:], qkv[:, 2 * d:], 3 * d, B, T, None, causal, tape, pk)
         if tape is not None:
             tape.append(("attn", p, dict(sv=sv, y=y, qkv=qkv, o=o, lse=lse, B=B, T=T, causal=causal, pk=pk)))
         return out
 
     def _cross_block(self, x, enc16, p, B, T, Tk, tape=None, kv=None, pend=None, pk=None):
         d = self.config.d_model
-        H = d // 64
         sv = {} if tape is not None else None
         x, y = self._ln_in(x, pend, p + "_layer_norm", sv)
         M = B * T if pk is None else pk.M
@@ -590,14 +598,7 @@ class WhisperForConditionalGeneration:
             wkv = self.wspan(p + ".k_proj.weight", p + ".v_proj.weight", (2 * d, d))
             bkv = self.wspan(p + ".k_proj.zero_bias", p + ".v_proj.bias", (2 * d,))
             self._lin(enc16, wkv, bkv, kv)
-        o = self._rows(M, d, self.act_dtype)
-        lse = torch.empty(H * M, dtype=torch.float32, device=self.device) if tape is not None else None
-        if pk is None:
-            F.attn_fwd(q, d, kv, 2 * d, kv[:, d:], 2 * d, o, d, lse, B, H, T, Tk, False, 0.125)
-        else:       # packed queries against the clip's dense Tk encoder rows
-            F.attn_fwd_varlen(q, d, kv, 2 * d, kv[:, d:], 2 * d, o, d, lse, pk.off, None, pk.B, H, M, pk.max_len, Tk,
-                              False, 0.125)
-        out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
+        out, o, lse = self._attn_fwd(x, p, q, d, kv, kv[:, d:], 2 * d, B, T, Tk, False, tape, pk)
         if tape is not None:
             tape.append(("cross", p, dict(sv=sv, y=y, q=q, kv=kv, o=o, lse=lse, B=B, T=T, Tk=Tk, pk=pk)))
         return out
@@ -889,26 +890,40 @@ class Backward:
         self.dX(dpre, m._w16(p + ".fc1.weight"), dy)
         self.ln(st["sv"], p + ".final_layer_norm", dy, dx)
 
-    def attn(self, p, st, dx):
+    def _out_proj(self, p, st, dx):
+        """out_proj backward of an attention block (its dW, db) -> (rows M, dO)."""
         m = self.m
         d = m.config.d_model
-        H = d // 64
-        B, T, pk = st["B"], st["T"], st.get("pk")
-        M = B * T if pk is None else pk.M
+        pk = st.get("pk")
+        M = st["B"] * st["T"] if pk is None else pk.M
         g = self._grad16(dx)
         self.dW(g, st["o"], m.gv(p + ".out_proj.weight"), M)
         self.db(g, (0, d), m.gv(p + ".out_proj.bias"))
         do = m._rows(M, d, m.act_dtype)
         self.dX(g, m._w16(p + ".out_proj.weight"), do)
+        return M, do
+
+    def _attn_bwd(self, st, q, ldq, k, v, ldkv, do, dq, lddq, dk, dv, lddkv, Tk, causal):
+        """dq, dk, dv of the block recorded in st (the arguments of the model's _attn_fwd; Tk None: self-attention)."""
+        d = self.m.config.d_model
+        H = d // 64
+        B, T, pk = st["B"], st["T"], st.get("pk")
+        if pk is None:
+            F.attn_bwd(q, ldq, k, ldkv, v, ldkv, st["o"], d, do, d, st["lse"], dq, lddq, dk, lddkv, dv, lddkv, B, H, T,
+                       T if Tk is None else Tk, causal, 0.125)
+        else:       # dense keys: every clip's dK / dV block is written (zeros for a clip without rows)
+            offk, Tk = (pk.off, pk.max_len) if Tk is None else (None, Tk)
+            F.attn_bwd_varlen(q, ldq, k, ldkv, v, ldkv, st["o"], d, do, d, st["lse"], dq, lddq, dk, lddkv, dv, lddkv,
+                              pk.off, offk, pk.B, H, pk.M, pk.max_len, Tk, causal, 0.125)
+
+    def attn(self, p, st, dx):
+        m = self.m
+        d = m.config.d_model
+        M, do = self._out_proj(p, st, dx)
         qkv = st["qkv"]
         dqkv = m._rows(M, 3 * d, m.act_dtype)
-        if pk is None:
-            F.attn_bwd(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, st["o"], d, do, d, st["lse"], dqkv, 3 * d,
-                       dqkv[:, d:], 3 * d, dqkv[:, 2 * d:], 3 * d, B, H, T, T, st["causal"], 0.125)
-        else:
-            F.attn_bwd_varlen(qkv, 3 * d, qkv[:, d:], 3 * d, qkv[:, 2 * d:], 3 * d, st["o"], d, do, d, st["lse"], dqkv,
-                              3 * d, dqkv[:, d:], 3 * d, dqkv[:, 2 * d:], 3 * d, pk.off, pk.off, pk.B, H, M, pk.max_len,
-                              pk.max_len, st["causal"], 0.125)
+        self._attn_bwd(st, qkv, 3 * d, qkv[:, d:], qkv[:, 2 * d:], 3 * d, do, dqkv, 3 * d, dqkv[:, d:], dqkv[:, 2 * d:],
+                       3 * d, None, st["causal"])
         self.dW(dqkv, st["y"], self.span_grad(p + ".q_proj.weight", p + ".v_proj.weight", (3 * d, d)), M)
         self.db(dqkv, (0, d), m.gv(p + ".q_proj.bias"))
         self.db(dqkv, (2 * d, 3 * d), m.gv(p + ".v_proj.bias"))
@@ -920,23 +935,12 @@ class Backward:
     def cross(self, p, st, dx, enc16, d_enc):
         m = self.m
         d = m.config.d_model
-        H = d // 64
-        B, T, Tk, pk = st["B"], st["T"], st["Tk"], st.get("pk")
-        M = B * T if pk is None else pk.M
-        g = self._grad16(dx)
-        self.dW(g, st["o"], m.gv(p + ".out_proj.weight"), M)
-        self.db(g, (0, d), m.gv(p + ".out_proj.bias"))
-        do = m._rows(M, d, m.act_dtype)
-        self.dX(g, m._w16(p + ".out_proj.weight"), do)
+        B, Tk = st["B"], st["Tk"]
+        M, do = self._out_proj(p, st, dx)
         kv = st["kv"]
         dq = m._rows(M, d, m.act_dtype)
         dkv = torch.empty(B * Tk, 2 * d, dtype=m.act_dtype, device=self.dev)
-        if pk is None:
-            F.attn_bwd(st["q"], d, kv, 2 * d, kv[:, d:], 2 * d, st["o"], d, do, d, st["lse"], dq, d, dkv, 2 * d,
-                       dkv[:, d:], 2 * d, B, H, T, Tk, False, 0.125)
-        else:       # every clip's dense dK / dV block is written (zeros for a clip without rows)
-            F.attn_bwd_varlen(st["q"], d, kv, 2 * d, kv[:, d:], 2 * d, st["o"], d, do, d, st["lse"], dq, d, dkv, 2 * d,
-                              dkv[:, d:], 2 * d, pk.off, None, pk.B, H, M, pk.max_len, Tk, False, 0.125)
+        self._attn_bwd(st, st["q"], d, kv, kv[:, d:], 2 * d, do, dq, d, dkv, dkv[:, d:], 2 * d, Tk, False)
         self.dW(dq, st["y"], m.gv(p + ".q_proj.weight"), M)
         self.db(dq, (0, d), m.gv(p + ".q_proj.bias"))
         dy = m._rows(M, d, m.act_dtype)

@@ -179,17 +179,37 @@ def layernorm_bwd(x, w, mean, rstd, dy, dx, dw, db, dx_accum=True, workspace=Non
     return dx
 
 
+def _attn_sym(name, q, q_side, k_side, lse, H, B, Tq, Tk, offq=None, offk=None, Mq=None):
+    """The checks of the four 16-bit attention wrappers -> the C symbol for q's dtype, or None when the call has no
+    rows to compute.  q_side / k_side: (tensor, ld, name) of the matrices that hold query / key rows.  Dense (Mq None):
+    B clips of Tq / Tk rows, lse [B][H][Tq].  Packed: offq [B+1] int32 device offsets, Mq query rows in all, Tq the
+    longest clip; offk is offq (packed keys, Tk = Tq) or None (dense keys); lse [H][Mq]."""
+    if Mq is None:
+        rows_q, rows_k, n_lse = B * Tq, B * Tk, B * H * Tq
+    else:
+        _need(offq, B + 1, "attn offq")
+        assert offq.dtype == torch.int32 and 0 <= Tq <= Mq
+        if offk is not None:
+            assert offk.data_ptr() == offq.data_ptr() and Tk == Tq, "packed keys: the self-attention case (offk is offq)"
+        rows_q, rows_k, n_lse = Mq, (B * Tk if offk is None else Mq), H * Mq
+        # the forward has nothing to do without queries; the backward still zeroes dK / dV of dense keys
+        if (rows_k if "bwd" in name else rows_q) <= 0:
+            return None
+    for side, rows in ((q_side, rows_q), (k_side, rows_k)):
+        for t, ld, nm in side:
+            assert t.dtype == q.dtype and t.dtype in HALF, nm
+            _need(t, (rows - 1) * ld + H * 64, f"{name} {nm}")
+    if lse is not None or "bwd" in name:
+        _need(lse, n_lse, f"{name} lse")
+    return f"tw_{name}_f16" if q.dtype == torch.float16 else f"tw_{name}"
+
+
 def attn_fwd(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, Tq, Tk, causal, scale):
     if q.dtype == torch.float32:
         return attn_fwd_f32(q, ldq, k, ldk, v, ldv, o, ldo, lse, B, H, Tq, Tk, causal, scale)
-    hd = 64
-    for t, ld, T, nm in ((q, ldq, Tq, "q"), (k, ldk, Tk, "k"), (v, ldv, Tk, "v"), (o, ldo, Tq, "o")):
-        assert t.dtype == q.dtype and t.dtype in HALF, nm
-        _need(t, (B * T - 1) * ld + H * hd, f"attn {nm}")
-    if lse is not None:
-        _need(lse, B * H * Tq, "attn lse")
-    call("tw_attn_fwd_f16" if q.dtype == torch.float16 else "tw_attn_fwd", q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse),
-         B, H, Tq, Tk, hd, int(causal), float(scale), _stream())
+    sym = _attn_sym("attn_fwd", q, ((q, ldq, "q"), (o, ldo, "o")), ((k, ldk, "k"), (v, ldv, "v")), lse, H, B, Tq, Tk)
+    call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse), B, H, Tq, Tk, 64,
+         int(causal), float(scale), _stream())
     return o
 
 
@@ -198,65 +218,38 @@ def attn_bwd(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, 
     if q.dtype == torch.float32:
         return attn_bwd_f32(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, dv, lddv, B, H, Tq, Tk,
                             causal, scale)
-    hd = 64
-    for t, ld, T, nm in ((q, ldq, Tq, "q"), (k, ldk, Tk, "k"), (v, ldv, Tk, "v"), (o, ldo, Tq, "o"),
-                         (do, lddo, Tq, "do"), (dq, lddq, Tq, "dq"), (dk, lddk, Tk, "dk"), (dv, lddv, Tk, "dv")):
-        assert t.dtype == q.dtype and t.dtype in HALF, nm
-        _need(t, (B * T - 1) * ld + H * hd, f"attn_bwd {nm}")
-    _need(lse, B * H * Tq, "attn lse")
+    sym = _attn_sym("attn_bwd", q, ((q, ldq, "q"), (o, ldo, "o"), (do, lddo, "do"), (dq, lddq, "dq")),
+                    ((k, ldk, "k"), (v, ldv, "v"), (dk, lddk, "dk"), (dv, lddv, "dv")), lse, H, B, Tq, Tk)
     if workspace is None or workspace.numel() < B * H * Tq:
         workspace = torch.empty(B * H * Tq, dtype=torch.float32, device=q.device)
-    call("tw_attn_bwd_f16" if q.dtype == torch.float16 else "tw_attn_bwd", q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(),
-         lddo, lse.data_ptr(), dq.data_ptr(), lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, B, H, Tq, Tk, hd,
-         int(causal), float(scale), workspace.data_ptr(), _stream())
-
-
-def _varlen_check(offq, offk, B, Mq, max_q, Tk):
-    """-> rows the key-side matrices hold: Mq for packed keys (offk is the query array), else dense B*Tk."""
-    _need(offq, B + 1, "attn offq")
-    assert offq.dtype == torch.int32 and 0 <= max_q <= Mq
-    if offk is None:
-        return B * Tk
-    assert offk.data_ptr() == offq.data_ptr() and Tk == max_q, "packed keys: the self-attention case (offk is offq)"
-    return Mq
+    call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(), lddo,
+         lse.data_ptr(), dq.data_ptr(), lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, B, H, Tq, Tk, 64, int(causal),
+         float(scale), workspace.data_ptr(), _stream())
 
 
 def attn_fwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, causal, scale):
     """attn_fwd over packed rows (16-bit only): offq [B+1] int32 device offsets of the clips' query rows, Mq their
     total and max_q the longest; offk = offq (packed keys, Tk = max_q) or None (dense keys, Tk each).  lse [H][Mq]."""
-    hd = 64
-    Mk = _varlen_check(offq, offk, B, Mq, max_q, Tk)
-    if Mq <= 0:
-        return o
-    for t, ld, rows, nm in ((q, ldq, Mq, "q"), (k, ldk, Mk, "k"), (v, ldv, Mk, "v"), (o, ldo, Mq, "o")):
-        assert t.dtype == q.dtype and t.dtype in HALF, nm
-        _need(t, (rows - 1) * ld + H * hd, f"attn_varlen {nm}")
-    if lse is not None:
-        _need(lse, H * Mq, "attn_varlen lse")
-    call("tw_attn_fwd_varlen_f16" if q.dtype == torch.float16 else "tw_attn_fwd_varlen", q.data_ptr(), ldq,
-         k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse), offq.data_ptr(), _ptr(offk), B, H, Mq,
-         max_q, Tk, hd, int(causal), float(scale), _stream())
+    sym = _attn_sym("attn_fwd_varlen", q, ((q, ldq, "q"), (o, ldo, "o")), ((k, ldk, "k"), (v, ldv, "v")), lse, H, B,
+                    max_q, Tk, offq, offk, Mq)
+    if sym is not None:
+        call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse),
+             offq.data_ptr(), _ptr(offk), B, H, Mq, max_q, Tk, 64, int(causal), float(scale), _stream())
     return o
 
 
 def attn_bwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, dv, lddv, offq, offk, B, H, Mq,
                     max_q, Tk, causal, scale):
     """attn_bwd over packed rows (see attn_fwd_varlen); with dense keys every clip's dK / dV block is written."""
-    hd = 64
-    Mk = _varlen_check(offq, offk, B, Mq, max_q, Tk)
-    if Mk <= 0:
+    sym = _attn_sym("attn_bwd_varlen", q, ((q, ldq, "q"), (o, ldo, "o"), (do, lddo, "do"), (dq, lddq, "dq")),
+                    ((k, ldk, "k"), (v, ldv, "v"), (dk, lddk, "dk"), (dv, lddv, "dv")), lse, H, B, max_q, Tk, offq,
+                    offk, Mq)
+    if sym is None:
         return
-    for t, ld, rows, nm in ((q, ldq, Mq, "q"), (k, ldk, Mk, "k"), (v, ldv, Mk, "v"), (o, ldo, Mq, "o"),
-                            (do, lddo, Mq, "do"), (dq, lddq, Mq, "dq"), (dk, lddk, Mk, "dk"), (dv, lddv, Mk, "dv")):
-        assert t.dtype == q.dtype and t.dtype in HALF, nm
-        if rows > 0:
-            _need(t, (rows - 1) * ld + H * hd, f"attn_bwd_varlen {nm}")
-    _need(lse, H * Mq, "attn_varlen lse")
     ws = torch.empty(max(H * Mq, 1), dtype=torch.float32, device=q.device)
-    call("tw_attn_bwd_varlen_f16" if q.dtype == torch.float16 else "tw_attn_bwd_varlen", q.data_ptr(), ldq,
-         k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(), lddo, lse.data_ptr(), dq.data_ptr(),
-         lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, offq.data_ptr(), _ptr(offk), B, H, Mq, max_q, Tk, hd,
-         int(causal), float(scale), ws.data_ptr(), _stream())
+    call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(), lddo,
+         lse.data_ptr(), dq.data_ptr(), lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, offq.data_ptr(), _ptr(offk), B,
+         H, Mq, max_q, Tk, 64, int(causal), float(scale), ws.data_ptr(), _stream())
 
 
 def kl_ce(s_logits, t_logits, labels, V, n_valid, T=2.0, ce_w=0.8, kl_w=1.0, grad_scale=1.0, dlogits=None,
