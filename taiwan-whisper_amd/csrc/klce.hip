@@ -20,14 +20,22 @@ struct Stats {
   float mt, ztt, a;      // teacher: max, sum exp((t-mt)/T), sum exp((t-mt)/T)*(t-s)
 };
 
+// The student's (ms, zt) and the teacher's (mt, ztt) go through one operation sequence, here and in the pass-1 loop, so
+// that equal rows give lsesT == lsetT bit for bit and q - p == 0 exactly: both merges are written in one form
+// (x * ex + y * ey with the same selects) and fma contraction is off in both places (the compiler had fused two
+// differently written sums differently, leaving an ulp between them).  Pass 2's s * invT - lsesT and t * invT - lsetT
+// are one expression on equal operands and need no pragma.
 __device__ __forceinline__ void merge(Stats& x, const Stats& y, float invT) {
+#pragma clang fp contract(off)
   const float ms = fmaxf(x.ms, y.ms);
   if (ms != -INFINITY) {
-    const float zx1 = x.ms == -INFINITY ? 0.f : x.z1 * __expf(x.ms - ms);
-    const float zy1 = y.ms == -INFINITY ? 0.f : y.z1 * __expf(y.ms - ms);
-    const float zxt = x.ms == -INFINITY ? 0.f : x.zt * __expf((x.ms - ms) * invT);
-    const float zyt = y.ms == -INFINITY ? 0.f : y.zt * __expf((y.ms - ms) * invT);
-    x.z1 = zx1 + zy1; x.zt = zxt + zyt; x.ms = ms;
+    const float ex1 = x.ms == -INFINITY ? 0.f : __expf(x.ms - ms);
+    const float ey1 = y.ms == -INFINITY ? 0.f : __expf(y.ms - ms);
+    const float ex = x.ms == -INFINITY ? 0.f : __expf((x.ms - ms) * invT);
+    const float ey = y.ms == -INFINITY ? 0.f : __expf((y.ms - ms) * invT);
+    x.z1 = x.z1 * ex1 + y.z1 * ey1;
+    x.zt = x.zt * ex + y.zt * ey;
+    x.ms = ms;
   }
   const float mt = fmaxf(x.mt, y.mt);
   if (mt != -INFINITY) {
@@ -70,6 +78,7 @@ __global__ __launch_bounds__(NT) void klce_kernel(const E* S, const E* __restric
   const float invT = 1.f / T;
   Stats st = {-INFINITY, 0.f, 0.f, -INFINITY, 0.f, 0.f};
   for (int c = tid; c < nch; c += NT) {
+#pragma clang fp contract(off)
     float sv[8], tv[8];
     load8(srow + c * 8, sv);
     load8(trow + c * 8, tv);
