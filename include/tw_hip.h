@@ -37,6 +37,9 @@ typedef void* tw_stream_t; /* hipStream_t */
 #define TW_GEMM_TILE256 512   /* force the 256x256 tile */
 #define TW_GEMM_TILE256x128 1024  /* force the 256x128 tile with the 3-stage LDS ring */
 #define TW_GEMM_TILE256PP 2048    /* force the 256x256 ping-pong kernel (a_trans = b_trans = 0 only) */
+#define TW_GEMM_NOSPLIT 16384     /* no split-K and no whole-rounds + tail split */
+#define TW_GEMM_TILE256x128_S2 262144  /* force the 256x128 tile with the 2-stage LDS ring */
+#define TW_GEMM_GROUP_M(g) ((g) << 24) /* force the tile order: runs of g (1..15) m-tiles */
 
 
 /* bf16 MFMA GEMM  C[b] = epi(alpha * A[b] . B[b]^T), A [M][K] (a_trans: [K][M]), B [N][K] (b_trans: [K][N]).
@@ -50,6 +53,21 @@ int tw_gemm_bf16(const void* A, int64_t lda, int a_trans, const void* B, int64_t
                  int64_t ldc, int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB, int64_t sC,
                  float alpha, const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype, int res_mod,
                  void* aux, int64_t ldaux, int64_t sAux, int flags, tw_stream_t stream);
+
+/* How tw_gemm_bf16 (is_f16 = 0) / tw_gemm_f16 (is_f16 = 1) would run a call: the same validation and the same
+ * planner, nothing launched, host only.  The arguments are the call's (without alpha and the stream); the pointers
+ * are looked at for their alignment only, never dereferenced.  cus > 0: plan for that many CUs without calling
+ * into HIP (works on a host without a GPU); cus = 0: the current device's count.  have_ws = 0: the plan of a call
+ * that cannot get the split-K workspace (inside a stream capture when the block would have to grow).
+ * out[6] = route, S (K chunks; 1 for the unsplit skinny kernel, 0 where K is not split), m_dp (m-tile rows of 256 on
+ * the persistent kernel in routes 3 and 4), split_tile (128 / 256 in route 2), group_m, epilogue kind.  Routes:
+ * 0 skinny, 1 skinny split-K, 2 dW split-K, 3 whole rounds + split-K tail, 4 whole rounds + 128x128 tail,
+ * 5 persistent 256x256, 6 persistent + fp16 edge strips, 7 128x128 2-stage, 8 128x128 4-stage ring, 9 256x256
+ * 2-stage, 10 256x128 3-stage ring, 11 256x128 2-stage ring; -1: nothing to compute.  Returns what the call would. */
+int tw_gemm_route(const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb, int b_trans, void* C,
+                  int64_t ldc, int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB, int64_t sC,
+                  const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype, int res_mod, void* aux,
+                  int64_t ldaux, int64_t sAux, int flags, int is_f16, int cus, int have_ws, int* out);
 
 /* Decode-step Linear for up to 4 rows (batch-1 long-form): C = epi(A . W^T), one output column per wave.
  * A = x [M][K] bf16, or LayerNorm(x) when ln_w != NULL (fp32 gamma ln_w / beta ln_b, eps; K % 256 == 0;

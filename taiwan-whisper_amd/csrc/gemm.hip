@@ -24,6 +24,9 @@ namespace {
 
 using namespace twg;
 
+// Block tile BMxBN, waves WMxWN (each (BM/WM)x(BN/WN)), one barrier per K-step.
+// blockIdx.x enumerates (m-tile, n-tile) pairs remapped so that consecutive tiles of one m-row
+// share an XCD (L2 reuse of the A panel; blocks b and b+8 share an XCD).
 // STAGES-deep LDS ring, prefetch distance STAGES-1; waits are counted (vmcnt = loads of the
 // stages allowed to stay in flight) and the barrier is a raw s_barrier, so in-flight LDS-DMA
 // survives it (a __syncthreads() would drain vmcnt(0)).
@@ -132,19 +135,16 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_kernel(GemmP p) {
 // Ping-pong 256x256 kernel for K-major A and B (the forward X·Wᵀ of every Linear).
 //
 // 8 waves as 2 (rows) x 4 (cols), each wave owns 128x64 of C = 4 quadrants of 64x32.  A K-tile
-// (BK = 64) is consumed in 4 phases, one quadrant per phase (16 MFMAs):
-//   q(0,0): read A-half 0 + B-quarter 0    q(0,1): read B-quarter 1
-//   q(1,1): read A-half 1                  q(1,0): read B-quarter 0 again
+// (BK = 64) is consumed in 2 phases of 32 MFMAs: A-half 0, then A-half 1, each against both
+// B-quarters (the schedule is described at the main loop).
 // LDS = 2 buffers (even / odd K-tile) x 4 regions of 16 KiB:
 //   A-half h    : rows  wr*128 + h*64 + [0,64)  for wr = 0,1   (the rows quadrant-row h reads)
 //   B-quarter q : cols  wc*64  + q*32 + [0,32)  for wc = 0..3  (the cols quadrant-col q reads)
-// so each region's last read in a K-tile is one phase (A-h0: 1, B-q1: 2, A-h1: 3, B-q0: 4), and
-// every phase restages exactly one region (2 LDS-DMA per lane) for the K-tile two ahead in the
-// same buffer, one phase after that region's last read (reads are retired by lgkmcnt(0) before
-// the barrier that ends the reading section).  Waits: vmcnt(6) at phases 4 and 8 = three
-// regions left in flight across the barrier (raw s_barrier, never __syncthreads()).
+// A region is restaged (2 LDS-DMA per lane) for the K-tile two ahead in the same buffer after its
+// last read (reads are retired by lgkmcnt(0) before the barrier that ends the reading section);
+// the waits are counted and the barrier is a raw s_barrier, never __syncthreads().
 // The two wave rows run one barrier apart (wave-row 1 takes an extra barrier up front): on each
-// SIMD (waves w and w+4) one wave issues its 16 MFMAs while the other issues LDS reads and DMA.
+// SIMD (waves w and w+4) one wave issues its MFMAs while the other issues LDS reads and DMA.
 // ---------------------------------------------------------------------------------------------
 constexpr int PP_REGION = 16384;
 
@@ -193,14 +193,16 @@ __device__ __forceinline__ void pp_stage_full(const bf16* base, int64_t ld, int 
 }
 
 // Epilogue of fragment rows MI0 .. MI1-1 of finished tile `ti` of this workgroup, then those accumulators
-// are zeroed for the next tile.  Debug flags: 4096 skips the stores, 1 << 20 stores every tile to tile 0.
+// are zeroed for the next tile.  The two diagnostic tests stay in the default build: without them the compiler
+// allocates the kernel's scalar registers differently and reloads spilled ones inside the main loop (6-8 more
+// instructions per K-tile pair; persistent forward shapes 0.5-1.4 % slower, the c3 step 0.35 %, same-box A/B).
 template <bool H, int KIND, int MI0, int MI1>
 __device__ __forceinline__ void pp_epi_part(const GemmP& p, f32x4 (&acc)[8][4], int ti, int wm, int wn, int lane,
                                             const bf16* braw) {
-  if (!(p.flags & 4096) || acc[MI0][0][0] != acc[MI0][0][0]) {
+  if (!(p.flags & F_DIAG_SKIP_STORES) || acc[MI0][0][0] != acc[MI0][0][0]) {
     int m0, n0, bz;
     pp_tile(p, ti, m0, n0, bz);
-    if (p.flags & (1 << 20)) { m0 = 0; n0 = 0; }
+    if (p.flags & F_DIAG_STORE_TILE0) { m0 = 0; n0 = 0; }
     epilogue_k<H, 256, 256, 2, 4, KIND, MI0, MI1, true>(p, acc, m0, n0, wm, wn, lane, bz, braw);
   }
 #pragma unroll
@@ -216,13 +218,14 @@ __device__ __forceinline__ void pp_epi_part(const GemmP& p, f32x4 (&acc)[8][4], 
 // pad K-tile stages zeros), so the next tile's first K-tiles are already in flight while the
 // finished tile's epilogue runs (between phases, beside the other wave-row's MFMAs).
 
-// PRIO (variant; flags bits 15-17 select it, see launch_pp): 0 = four 16-MFMA phases per K-tile,
-// prio 1 around each MFMA phase; 1 = the same with static prio 1 for the trailing wave row
-// (waves 4-7), no flips; 2 = diagnostic: every MFMA phase issued twice (wrong results; measures
-// the fixed per-phase cost); 4 = two 32-MFMA phases per K-tile (default: +4-8 % main loop)
+// DIAG: PP_PROD is the kernel; the others are subtraction variants of its main loop (wrong results), instantiated
+// by a diagnostic build (-DTW_PP_DIAG_VARIANTS) only, where flags bits 15-17 select them (launch_pp).
 // KF: K is a multiple of 64 (every launch of the model's shapes but the conv stem's K = 240): staging without per-lane
 // bound arithmetic (pp_stage_full).  KF = false keeps the checked stager for a K tail (generic epilogue only).
-template <bool H, int PRIO, int KIND = -1, bool KF = true>
+// PP_NO_A1: A-half 1 not read (LDS-read cost); PP_NO_RESTAGE: no restaging in the main loop (timing of everything
+// but the DMA); PP_NO_WAIT: no counted waits
+enum { PP_PROD = 0, PP_NO_A1 = 5, PP_NO_RESTAGE = 6, PP_NO_WAIT = 7 };
+template <bool H, int DIAG, int KIND = -1, bool KF = true>
 __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
   // + 2 x 1 KiB: the bias slice of the current tile (by tile parity), for the fast epilogue (one array:
   // a second __shared__ object can make the compiler drain vmcnt before LDS reads)
@@ -253,9 +256,9 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
     int m0 = 0, n0 = 0, bz = 0;
     const bool live = i < my_tiles && pp_tile(p, i, m0, n0, bz);
 #ifdef TW_PP_DIAG_VARIANTS
-    // diagnostic build only, flag 1 << 22: every tile stages the panels of its workgroup's XCD-first tile (A rows and
-    // B columns of one 256 x 256 block per XCD, L2-resident): the main loop without L2 misses (wrong results)
-    if (p.flags & (1 << 22)) { m0 = p.M >= 2048 ? ((int)blockIdx.x & 7) * 256 : 0; n0 = 0; bz = 0; }
+    // every tile stages the panels of its workgroup's XCD-first tile (A rows and B columns of one 256 x 256 block
+    // per XCD, L2-resident): the main loop without L2 misses (wrong results)
+    if (p.flags & F_DIAG_L2_PANELS) { m0 = p.M >= 2048 ? ((int)blockIdx.x & 7) * 256 : 0; n0 = 0; bz = 0; }
 #endif
     pa = p.A + bz * p.sA + (int64_t)m0 * p.lda;
     pb = p.B + bz * p.sB + (int64_t)n0 * p.ldb;
@@ -278,24 +281,21 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
     }
   };
 
-  // PRIO 6: diagnostic, no restaging in the main loop (timing of everything but the DMA)
+  // the main loop's restaging and waits (the diagnostic variants drop one of them)
   auto stg = [&](const bf16* pa, const bf16* pb, int rows, int cols, int kl, int kt, int buf, int r) {
-    if constexpr (PRIO != 6) stage(pa, pb, rows, cols, kl, kt, buf, r);
+    if constexpr (DIAG != PP_NO_RESTAGE) stage(pa, pb, rows, cols, kl, kt, buf, r);
   };
-  bf16x8 a[2][4], bb[2][2];
-  bf16x8 bq[2][2][2];                        // PRIO 4: both B-quarters of the K-tile
+  auto wait6 = [] { if constexpr (DIAG != PP_NO_WAIT) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); };
+  auto wait2 = [] { if constexpr (DIAG != PP_NO_WAIT) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); };
+  bf16x8 a[2][4];
+  bf16x8 bq[2][2][2];                        // both B-quarters of the K-tile
   auto rdA = [&](int b, int h) {
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) a[kk][mi] = frag_k(reg(b, h), wm * 64 + mi * 16, kk, lane);
   };
-  auto rdB = [&](int b, int qq) {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) bb[kk][ni] = frag_k(reg(b, 2 + qq), wn * 32 + ni * 16, kk, lane);
-  };
+  auto rdA1 = [&](int b) { if constexpr (DIAG != PP_NO_A1) rdA(b, 1); };
   auto rdB2 = [&](int b) {
 #pragma unroll
     for (int qq = 0; qq < 2; ++qq)
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
   };
-  // PRIO 4: one phase = one A-half x both B-quarters (32 MFMAs)
+  // one phase = one A-half x both B-quarters (32 MFMAs)
   auto mma2 = [&](int qm) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     sync();
@@ -327,40 +327,18 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
     __builtin_amdgcn_s_setprio(0);
     sync();
   };
-  auto mma = [&](int qm, int qn) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    sync();
-    if constexpr (PRIO == 0 || PRIO == 2) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int rep = 0; rep < (PRIO == 2 ? 2 : 1); ++rep)
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[qm * 4 + mi][qn * 2 + ni] =
-              mma16<H>(bb[kk][ni], a[kk][mi], acc[qm * 4 + mi][qn * 2 + ni]);
-    if constexpr (PRIO == 0 || PRIO == 2) __builtin_amdgcn_s_setprio(0);
-    sync();
-  };
 
-  // prologue: K-tile 0 whole into buffer 0, K-tile 1 without B-quarter 0 into buffer 1
+  // prologue: K-tile 0 whole into buffer 0, K-tile 1 without its A-half 1 (staged in the first phase) into buffer 1
   const bf16 *cpa, *cpb;                     // current tile (see tile_info)
   int cr, cc, ck;
   tile_info(0, cpa, cpb, cr, cc, ck);
   int kt = 0;
   stage(cpa, cpb, cr, cc, ck, 0, 0, 0); stage(cpa, cpb, cr, cc, ck, 0, 0, 1);
   stage(cpa, cpb, cr, cc, ck, 0, 0, 2); stage(cpa, cpb, cr, cc, ck, 0, 0, 3);
-  if constexpr (PRIO >= 3) {                 // K-tile 1 without its A-half 1 (staged in the first phase)
-    stage(cpa, cpb, cr, cc, ck, 1, 1, 0); stage(cpa, cpb, cr, cc, ck, 1, 1, 2); stage(cpa, cpb, cr, cc, ck, 1, 1, 3);
-  } else {
-    stage(cpa, cpb, cr, cc, ck, 1, 1, 0); stage(cpa, cpb, cr, cc, ck, 1, 1, 3); stage(cpa, cpb, cr, cc, ck, 1, 1, 1);
-  }
+  stage(cpa, cpb, cr, cc, ck, 1, 1, 0); stage(cpa, cpb, cr, cc, ck, 1, 1, 2); stage(cpa, cpb, cr, cc, ck, 1, 1, 3);
   asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
   sync();
   if (wm == 1) sync();                       // stagger the wave rows by one barrier
-  if constexpr (PRIO == 1) { if (wm == 1) __builtin_amdgcn_s_setprio(1); }
 
   for (int g = 0; g < total; g += 2) {
     // K-tiles g, g+1 = (cur, kt), (cur, kt+1); g+2, g+3 = (nxt, k2), (nxt, k2+1)
@@ -371,53 +349,38 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmP p) {
       tile_info(si + 1, npa, npb, nr, nc, nkl);
       k2 = 0;
     }
-    if constexpr (PRIO >= 3) {
-      // Two phases per K-tile (A-half 0, then A-half 1, each against both B-quarters): the load
-      // segment before phase X reads A0, B0, B1 and stages A1 of the next K-tile; the one before
-      // phase Y reads A1 and stages A0, B0, B1 of the K-tile two ahead (their last readers, the
-      // other wave row's X-segment, finished one barrier earlier).  Waits, counted: at an X
-      // segment the A1 staged one segment-pair ago (6 DMA staged since), at a Y segment the
-      // A0/B0/B1 staged one pair ago (2 since) — each published by the barriers before its
-      // readers' segments.
-      if constexpr (PRIO != 7) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // PRIO 7: diagnostic, no waits
-      rdA(0, 0); rdB2(0); stg(cpa, cpb, cr, cc, ck, kt + 1, 1, 1);
-      // a tile's first K-tile pair: wave 0 stages its 256 bias words (LDS-DMA, no registers).  The next-but-one
-      // counted wait of wave 0 covers it and a barrier follows, long before the tile's epilogue reads it;
-      // the extra DMA only makes wave 0's counted waits stricter.
-      if (kt == 0 && (p.flags & F_BIAS) && wave == 0) {
-        int m0, n0, bz;
-        if (pp_tile(p, si, m0, n0, bz)) {
-          const int c = n0 + lane * 8;                          // 8 words per lane, lanes 0..31
-          const uint32_t o = (lane < 32 && c < p.N) ? (uint32_t)(c * 2) : TW_OOB;
-          buf_load_lds16(make_rsrc(p.bias), smem + 8 * PP_REGION + (si & 1) * 1024, o);
-        }
+    // Two phases per K-tile (A-half 0, then A-half 1, each against both B-quarters): the load
+    // segment before phase X reads A0, B0, B1 and stages A1 of the next K-tile; the one before
+    // phase Y reads A1 and stages A0, B0, B1 of the K-tile two ahead (their last readers, the
+    // other wave row's X-segment, finished one barrier earlier).  Waits, counted: at an X
+    // segment the A1 staged one segment-pair ago (6 DMA staged since), at a Y segment the
+    // A0/B0/B1 staged one pair ago (2 since) — each published by the barriers before its
+    // readers' segments.
+    wait6();
+    rdA(0, 0); rdB2(0); stg(cpa, cpb, cr, cc, ck, kt + 1, 1, 1);
+    // a tile's first K-tile pair: wave 0 stages its 256 bias words (LDS-DMA, no registers).  The next-but-one
+    // counted wait of wave 0 covers it and a barrier follows, long before the tile's epilogue reads it;
+    // the extra DMA only makes wave 0's counted waits stricter.
+    if (kt == 0 && (p.flags & F_BIAS) && wave == 0) {
+      int m0, n0, bz;
+      if (pp_tile(p, si, m0, n0, bz)) {
+        const int c = n0 + lane * 8;                          // 8 words per lane, lanes 0..31
+        const uint32_t o = (lane < 32 && c < p.N) ? (uint32_t)(c * 2) : TW_OOB;
+        buf_load_lds16(make_rsrc(p.bias), smem + 8 * PP_REGION + (si & 1) * 1024, o);
       }
-      mma2(0);
-      if constexpr (PRIO != 7) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      if constexpr (PRIO == 4 || PRIO == 3) rdA(0, 1);      // PRIO 5: diagnostic, A-half 1 not read (LDS-read cost)
-      stg(npa, npb, nr, nc, nkl, k2, 0, 0); stg(npa, npb, nr, nc, nkl, k2, 0, 2); stg(npa, npb, nr, nc, nkl, k2, 0, 3);
-      mma2(1);
-      if constexpr (PRIO != 7) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");   // PRIO 7: diagnostic, no waits
-      rdA(1, 0); rdB2(1); stg(npa, npb, nr, nc, nkl, k2, 0, 1);
-      mma2(0);
-      if constexpr (PRIO != 7) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      if constexpr (PRIO == 4 || PRIO == 3) rdA(1, 1);
-      stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 0); stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 2); stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 3);
-      mma2(1);
-    } else {
-    // even K-tile g from buffer 0
-    rdB(0, 0); rdA(0, 0); stage(cpa, cpb, cr, cc, ck, kt + 1, 1, 2);  mma(0, 0);
-    rdB(0, 1);            stage(npa, npb, nr, nc, nkl, k2, 0, 0);     mma(0, 1);
-    rdA(0, 1);            stage(npa, npb, nr, nc, nkl, k2, 0, 3);     mma(1, 1);
-    rdB(0, 0);            stage(npa, npb, nr, nc, nkl, k2, 0, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");            mma(1, 0);
-    // odd K-tile g+1 from buffer 1
-    rdB(1, 0); rdA(1, 0); stage(npa, npb, nr, nc, nkl, k2, 0, 2);     mma(0, 0);
-    rdB(1, 1);            stage(npa, npb, nr, nc, nkl, k2 + 1, 1, 0); mma(0, 1);
-    rdA(1, 1);            stage(npa, npb, nr, nc, nkl, k2 + 1, 1, 3); mma(1, 1);
-    rdB(1, 0);            stage(npa, npb, nr, nc, nkl, k2 + 1, 1, 1);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");            mma(1, 0);
     }
+    mma2(0);
+    wait2();
+    rdA1(0);
+    stg(npa, npb, nr, nc, nkl, k2, 0, 0); stg(npa, npb, nr, nc, nkl, k2, 0, 2); stg(npa, npb, nr, nc, nkl, k2, 0, 3);
+    mma2(1);
+    wait6();
+    rdA(1, 0); rdB2(1); stg(npa, npb, nr, nc, nkl, k2, 0, 1);
+    mma2(0);
+    wait2();
+    rdA1(1);
+    stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 0); stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 2); stg(npa, npb, nr, nc, nkl, k2 + 1, 1, 3);
+    mma2(1);
     if (last) {                                                 // tile finished
       pp_epi_part<H, KIND, 0, 8>(p, acc, si, wm, wn, lane, (const bf16*)(smem + 8 * PP_REGION + (si & 1) * 1024));
       ++si;
@@ -645,52 +608,58 @@ int pick_epilogue(const GemmP& p, int batch) {
   return EPI_GENERIC;
 }
 
-// the production variants are specialised on the epilogue kind (one fast epilogue + the generic one for
-// ragged tiles per kernel: the split epilogue's three inlined parts stay within the register budget)
-template <bool H, int PRIO>
-void launch_pp_kind(const GemmP& p, int grid, hipStream_t stream) {
-  if (p.K % BK) {     // a K tail (the conv stem's K = 240): the checked stager with the generic epilogue
-    hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_GENERIC, false>), dim3(grid), dim3(512), 0, stream, p);
-    return;
-  }
-  switch (p.epi) {
-    case EPI_STORE_BF16: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_STORE_BF16>), dim3(grid), dim3(512), 0, stream, p); break;
-    case EPI_STORE_F32: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_STORE_F32>), dim3(grid), dim3(512), 0, stream, p); break;
-    case EPI_GELU: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_GELU>), dim3(grid), dim3(512), 0, stream, p); break;
-    case EPI_GELU_AUX: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_GELU_AUX>), dim3(grid), dim3(512), 0, stream, p); break;
-    case EPI_RES_BF16: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_RES_BF16>), dim3(grid), dim3(512), 0, stream, p); break;
-    case EPI_RES_F32: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_RES_F32>), dim3(grid), dim3(512), 0, stream, p); break;
-    default: hipLaunchKernelGGL((gemm_pp_kernel<H, PRIO, EPI_GENERIC>), dim3(grid), dim3(512), 0, stream, p); break;
-  }
-}
-
-template <bool H>
-void launch_pp(GemmP p, int batch, hipStream_t stream) {
+// CUs of the current device (at least 8; 8 when there is no device), asked once.  The persistent kernel runs on
+// pp_workgroups(cus) workgroups, a multiple of 8 (one share per XCD); the planner counts rounds in the same unit.
+int device_cus() {
   static const int cus = [] {
     int dev = 0, n = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return n >= 8 ? n : 8;
   }();
+  return cus;
+}
+constexpr int pp_workgroups(int cus) { return cus & ~7; }
+
+// the persistent kernel is specialised on the epilogue kind (one fast epilogue + the generic one for
+// ragged tiles per kernel: the split epilogue's three inlined parts stay within the register budget)
+template <bool H>
+void launch_pp_kind(const GemmP& p, int grid, hipStream_t stream) {
+  if (p.K % BK) {     // a K tail (the conv stem's K = 240): the checked stager with the generic epilogue
+    hipLaunchKernelGGL((gemm_pp_kernel<H, PP_PROD, EPI_GENERIC, false>), dim3(grid), dim3(512), 0, stream, p);
+    return;
+  }
+#define TW_PP(KIND_) hipLaunchKernelGGL((gemm_pp_kernel<H, PP_PROD, KIND_>), dim3(grid), dim3(512), 0, stream, p)
+  switch (p.epi) {
+    case EPI_STORE_BF16: TW_PP(EPI_STORE_BF16); break;
+    case EPI_STORE_F32: TW_PP(EPI_STORE_F32); break;
+    case EPI_GELU: TW_PP(EPI_GELU); break;
+    case EPI_GELU_AUX: TW_PP(EPI_GELU_AUX); break;
+    case EPI_RES_BF16: TW_PP(EPI_RES_BF16); break;
+    case EPI_RES_F32: TW_PP(EPI_RES_F32); break;
+    default: TW_PP(EPI_GENERIC); break;
+  }
+#undef TW_PP
+}
+
+template <bool H>
+void launch_pp(GemmP p, int batch, hipStream_t stream) {
+  const int cus = device_cus();
   p.tiles_n = (p.N + 255) / 256;
   p.tiles_mn = p.tiles_n * ((p.M + 255) / 256);
   p.tiles_total = p.tiles_mn * batch;
-  int grid = p.tiles_total <= cus ? p.tiles_total : (cus & ~7);
-  if (p.flags & 8192) grid = p.tiles_total;   // diagnostic: one tile per workgroup
-  // default: two 32-MFMA phases per K-tile (PRIO 4); flags bits 15-17 select the diagnostic variants
-  // (the round-2 variants PRIO 0/1/2/5/6/7 stay in the source but are instantiated only in a diagnostic build:
-  // each is a full copy of the kernel; -DTW_PP_DIAG_VARIANTS brings them back, tools/bench_pp_prio.py)
-  switch ((p.flags >> 15) & 7) {
+  int grid = p.tiles_total <= cus ? p.tiles_total : pp_workgroups(cus);
 #ifdef TW_PP_DIAG_VARIANTS
-    case 1: hipLaunchKernelGGL((gemm_pp_kernel<H, 0>), dim3(grid), dim3(512), 0, stream, p); break;
-    case 2: hipLaunchKernelGGL((gemm_pp_kernel<H, 2>), dim3(grid), dim3(512), 0, stream, p); break;
-    case 3: hipLaunchKernelGGL((gemm_pp_kernel<H, 1>), dim3(grid), dim3(512), 0, stream, p); break;
-    case 5: hipLaunchKernelGGL((gemm_pp_kernel<H, 5>), dim3(grid), dim3(512), 0, stream, p); break;
-    case 6: hipLaunchKernelGGL((gemm_pp_kernel<H, 6>), dim3(grid), dim3(512), 0, stream, p); break;
-    case 7: hipLaunchKernelGGL((gemm_pp_kernel<H, 7>), dim3(grid), dim3(512), 0, stream, p); break;
-#endif
-    default: launch_pp_kind<H, 4>(p, grid, stream); break;
+  // each main-loop variant is a full copy of the kernel (runtime epilogue kind); tools/bench_pp_prio.py
+  if (p.flags & F_DIAG_TILE_PER_WG) grid = p.tiles_total;
+  switch ((p.flags >> F_DIAG_VARIANT_SHIFT) & 7) {
+    case PP_NO_A1: hipLaunchKernelGGL((gemm_pp_kernel<H, PP_NO_A1>), dim3(grid), dim3(512), 0, stream, p); return;
+    case PP_NO_RESTAGE: hipLaunchKernelGGL((gemm_pp_kernel<H, PP_NO_RESTAGE>), dim3(grid), dim3(512), 0, stream, p); return;
+    case PP_NO_WAIT: hipLaunchKernelGGL((gemm_pp_kernel<H, PP_NO_WAIT>), dim3(grid), dim3(512), 0, stream, p); return;
+    default: break;
   }
+#endif
+  launch_pp_kind<H>(p, grid, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -758,7 +727,58 @@ void* splitk_workspace(hipStream_t stream, size_t bytes) {
 }
 #endif
 
-int pp_grid_cus();
+}  // namespace
+
+// the same per-device block for other stream-ordered scratch users (decode attention split partials)
+#ifndef TW_GEMM_TU_F16
+void* tw_device_workspace(hipStream_t stream, size_t bytes) { return splitk_workspace(stream, bytes); }
+#endif
+
+namespace {
+
+// ---------------------------------------------------------------------------------------------
+// Host routing: plan_gemm() decides how a product runs (a pure function of the call, the CU count and
+// whether the split-K workspace is to be had), gemm_run() asks for the workspace and launches the plan.
+// The codes are part of the C ABI (tw_gemm_route, include/tw_hip.h).
+// ---------------------------------------------------------------------------------------------
+enum class Route : int {
+  Skinny = 0,            // weight-streaming kernel (decode-step Linears, M <= 128)
+  SkinnySplitK = 1,      // ... with the K range split over S workgroups + skinny_reduce_kernel
+  SplitKDw = 2,          // dW: S K-chunks on the 128x128 or 256x256 kernel (split_tile) + splitk_reduce_kernel
+  RoundsSkTail = 3,      // m_dp m-tile rows persistent + the rest as S split-K chunks + sk_reduce_kernel
+  RoundsDpTail = 4,      // m_dp m-tile rows persistent + the rest as 128x128 tiles on the 4-stage ring
+  Persistent = 5,        // 256x256 ping-pong kernel
+  PersistentEdges = 6,   // fp16: whole 256x256 tiles persistent + edge strips on the 128x128 kernel
+  T128 = 7,              // 128x128, 2 stages
+  T128Ring4 = 8,         // 128x128, 4-stage ring
+  T256 = 9,              // 256x256, 2 stages
+  T256x128S3 = 10,       // 256x128, 3-stage ring (forced only)
+  T256x128S2 = 11,       // 256x128, 2-stage ring (forced only)
+};
+
+struct GemmPlan {
+  Route route;
+  int S;            // K chunks of the skinny (1: unsplit), dW and split-K-tail routes; 0 elsewhere
+  int m_dp;         // RoundsSkTail / RoundsDpTail: m-tile rows (of 256) on the persistent kernel
+  int split_tile;   // SplitKDw: 128 or 256
+  int group_m;      // tile order (GemmP::group_m)
+  int epi;          // fast epilogue kind (GemmP::epi)
+  int64_t tiles;    // tiles per batch entry of the base tile: must fit the kernels' 32-bit tile ids (plan_fits)
+};
+
+bool plan_fits(const GemmPlan& pl, int batch) {
+  return pl.tiles <= 0x7fffffff && pl.tiles * batch <= 0x7fffffff && batch <= 65535;
+}
+
+// bytes of fp32 split-K partials the plan needs (0: none)
+size_t plan_ws_bytes(const GemmPlan& pl, const GemmP& p) {
+  switch (pl.route) {
+    case Route::SkinnySplitK:
+    case Route::SplitKDw: return (size_t)pl.S * p.M * p.N * sizeof(float);
+    case Route::RoundsSkTail: return (size_t)pl.S * (p.M - pl.m_dp * 256) * p.N * sizeof(float);
+    default: return 0;
+  }
+}
 
 // S for a dW-shaped call, 0 = no split: fewer than 512 128x128 tiles, K split into S equal chunks; fp32 output, flags
 // within {ROUND, ACCUM}.  The 128x128 split kernel holds two workgroups per CU (64 KiB of LDS each), so a grid of
@@ -769,21 +789,20 @@ int pp_grid_cus();
 // Powers of two before: c2's encoder 768 x 3072 weight gradients -- 144 tiles, K = 48 000 -- ran S = 4, 576
 // workgroups = 1.125 rounds of 12 000 k; with the 128 tile alone S = 10, with the 256 tile S = 6 on 216 workgroups.
 // c2 +1.3 %, c3 +0.3 % same-box, profiles/r06_al_ab.log.  Each chunk's fp32 sum is regrouped, as any split.)
-int splitk_factor(const GemmP& p, int batch, int a_trans, int b_trans, int* tile) {
+int splitk_factor(const GemmP& p, int batch, bool a_trans, bool b_trans, int64_t cus, int* tile) {
+  static const double R = [] {                     // (the one piece of process state the planner reads)
+    const char* e = getenv("TW_SK256_R");
+    return e ? atof(e) : 1.4;
+  }();
   *tile = 128;
   if (!a_trans || !b_trans || batch != 1 || p.c_dtype != TW_F32) return 0;
   if (p.flags & ~(F_ROUND | F_ACCUM) & 0xff) return 0;
   if ((p.N & 3) || (p.ldc & 3) || ((uintptr_t)p.C & 15)) return 0;
   const int64_t tiles = (int64_t)((p.M + 127) / 128) * ((p.N + 127) / 128);
   if (tiles >= 512) return 0;
-  const int64_t cus = pp_grid_cus();
   const int64_t slots = 2 * cus;
   // time units: one CU's 128x128 x 1k of work at the 128-tile rate.  A 128-tile round holds two workgroups per CU
   // (2 units per k); a 256-tile round one workgroup of four times the area at R times the 128-tile rate.
-  static const double R = [] {
-    const char* e = getenv("TW_SK256_R");
-    return e ? atof(e) : 1.4;
-  }();
   const int64_t tiles256 = (int64_t)((p.M + 255) / 256) * ((p.N + 255) / 256);
   double best_cost = (double)((tiles + slots - 1) / slots) * 2.0 * p.K;   // unsplit: rounds x K
   int best = 0;
@@ -800,47 +819,17 @@ int splitk_factor(const GemmP& p, int batch, int a_trans, int b_trans, int* tile
   return best;
 }
 
-template <bool H, bool AT, bool BT>
-void dispatch(GemmP p, int batch, hipStream_t stream, int tile) {
-  if constexpr (H && (AT || BT)) {
-    // fp16 training's dX / dW products: the 2-stage 256x256 and 128x128 tiles only (the 256x128 rings are forced
-    // A/B variants of the bf16 kernels; not instantiating them for fp16 keeps the library's build time down)
-    if (tile == 256) launch<H, AT, BT, 256, 256, 2, 4, 2>(p, batch, stream);
-    else launch<H, AT, BT, 128, 128, 2, 2, 2>(p, batch, stream);
-    return;
-  }
-  if (tile == 2562 && !AT && !BT) launch_pp<H>(p, batch, stream);
-  else if (tile == 1284) {
-    if constexpr (!AT && !BT) launch<H, AT, BT, 128, 128, 2, 2, 4>(p, batch, stream);   // 4-stage ring
-  }
-  else if (tile == 256) launch<H, AT, BT, 256, 256, 2, 4, 2>(p, batch, stream);
-  else if (tile == 2561) launch<H, AT, BT, 256, 128, 4, 2, 3>(p, batch, stream);
-  else if (tile == 2563) launch<H, AT, BT, 256, 128, 4, 2, 2>(p, batch, stream);
-  else launch<H, AT, BT, 128, 128, 2, 2, 2>(p, batch, stream);
-}
-
-int pp_grid_cus() {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n >= 8 ? n : 8;
-  }();
-  return cus & ~7;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Data-parallel + split-K tail for the mid-sized forward GEMMs (the decoder's N = 1280 Linears at
 // M = 64 x 447: 560 256-tiles = 2.19 rounds of the 256 persistent workgroups).  The m-tile rows that
 // fill whole rounds run as ordinary persistent tiles (full epilogue); the remaining m-tile rows are cut
 // into S equal K chunks run as S batch entries of the same kernel into fp32 partials (one round),
-// then skinny_reduce_kernel sums the chunks in order and applies the full epilogue to those rows.
-// Returns S (0 = no plan: the caller takes the 128x128 path).  Numerics: the tail rows' fp32 sum over
-// K is regrouped by chunk (as the dW split-K); every other row is the unsplit kernel's.
+// then sk_reduce_kernel sums the chunks in order and applies the full epilogue to those rows.
+// Returns S (0 = no plan: the caller takes the rules that follow).  Numerics: the tail rows' fp32 sum over
+// K is regrouped by chunk (as the dW split-K); every other row is the unsplit kernel's.  G = persistent workgroups.
 // ---------------------------------------------------------------------------------------------
-int sk_tail_plan(const GemmP& p, int batch, int& m_dp) {
+int sk_tail_plan(const GemmP& p, int batch, int G, int& m_dp) {
   if (batch != 1 || p.res_mod != 0 || (p.N & 3) || (p.ldc & 3) || ((uintptr_t)p.C & 15)) return 0;
-  const int G = pp_grid_cus();
   const int tn = (p.N + 255) / 256, tm = (p.M + 255) / 256;
   const int64_t T = (int64_t)tn * tm;
   if (T < G && p.M >= 256) {
@@ -862,45 +851,6 @@ int sk_tail_plan(const GemmP& p, int batch, int& m_dp) {
   return best;
 }
 
-template <bool H>
-int launch_sk_tail(GemmP p, int S, int m_dp, hipStream_t stream) {
-  const int Mt = p.M - m_dp * 256;
-  const size_t bytes = (size_t)S * Mt * p.N * sizeof(float);
-  float* ws = (float*)splitk_workspace(stream, bytes);
-  if (!ws) return 0;
-  if (m_dp > 0) {
-    GemmP d = p;                                       // whole rounds: the unsplit kernel
-    d.M = m_dp * 256;
-    launch_pp<H>(d, 1, stream);
-    TW_CHECK_LAUNCH();
-  }
-  GemmP q = p;                                         // tail rows: S K-chunks -> fp32 partials
-  const int64_t r0 = (int64_t)m_dp * 256;
-  q.A = p.A + r0 * p.lda;
-  q.M = Mt;
-  q.K = p.K / S;
-  q.sA = q.K;                                          // chunk s starts at column s*K/S of A and B
-  q.sB = q.K;
-  q.C = ws; q.ldc = p.N; q.sC = (int64_t)Mt * p.N; q.c_dtype = TW_F32;
-  q.alpha = 1.f; q.flags = 0; q.bias = nullptr; q.res = nullptr; q.aux = nullptr; q.ws = nullptr;
-  q.group_m = 1;
-  q.epi = pick_epilogue(q, S);
-  launch_pp<H>(q, S, stream);
-  TW_CHECK_LAUNCH();
-  GemmP r = p;                                         // ordered chunk sum + the full epilogue
-  const int csz = p.c_dtype == TW_BF16 ? 2 : 4;
-  r.C = (char*)p.C + r0 * p.ldc * csz;
-  if (p.res) r.res = (const char*)p.res + r0 * p.ldr * (p.res_dtype == TW_BF16 ? 2 : 4);
-  if (p.aux) r.aux = p.aux + r0 * p.ldaux;
-  r.M = Mt;
-  r.ws = ws;
-  const int64_t work = (int64_t)Mt * (p.N / 4);
-  hipLaunchKernelGGL(sk_reduce_kernel<H>, dim3((int)std::min<int64_t>((work + 255) / 256, 4096)), dim3(256), 0,
-                     stream, r, S);
-  TW_CHECK_LAUNCH();
-  return 1;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Whole rounds persistent + a 128x128 tail: for grids whose last round of 256-tiles would leave most of the
 // persistent kernel's workgroups idle (the decoder's N = 1280 projections at M = 64 x 447: 560 256-tiles = 2.19
@@ -908,9 +858,8 @@ int launch_sk_tail(GemmP p, int S, int m_dp, hipStream_t stream) {
 // kernel and the remaining rows as 128x128 tiles on the 4-stage ring -- when they fit one round of it.  Both
 // kernels accumulate every output in the same K order (tests/test_kernels_gpu.py forced-tile identity), so the
 // result is bit-identical to either kernel alone.  Returns 0 (no plan) or 1, m_dp = m-tile rows of whole rounds.
-int dp_tail_plan(const GemmP& p, int batch, int& m_dp) {
+int dp_tail_plan(const GemmP& p, int batch, int G, int& m_dp) {
   if (batch != 1 || p.res_mod != 0) return 0;
-  const int G = pp_grid_cus();
   const int tn = (p.N + 255) / 256, tm = (p.M + 255) / 256;
   const int64_t T = (int64_t)tn * tm;
   if (T < G || T >= 8 * G) return 0;
@@ -922,24 +871,215 @@ int dp_tail_plan(const GemmP& p, int batch, int& m_dp) {
   return (m_dp > 0 && rows > 0 && t128 <= G) ? 1 : 0;
 }
 
+// The plan of a validated call (p: every field of the call filled in; group_m, epi and the tile counts are the
+// plan's to decide).  No HIP call, no allocation: `cus` is device_cus() or the caller's figure, `have_ws` says whether
+// a route that needs the split-K workspace may be chosen -- without it the rules after that route decide, which is
+// what a call inside a stream capture gets when the workspace would have to grow.
+GemmPlan plan_gemm(const GemmP& p, int batch, bool a_trans, bool b_trans, bool H, int cus, bool have_ws) {
+  const int M = p.M, N = p.N, K = p.K, flags = p.flags;
+  const bool kmajor = !a_trans && !b_trans;
+  const int64_t G = pp_workgroups(cus);
+  GemmPlan pl = {Route::T128, 0, 0, 0, 1, EPI_GENERIC, 0};
+  // tile order: runs of 8 m-tiles walked n-tile by n-tile for the tall, short-K forward GEMMs (the
+  // encoder's M = B x 1500 projections: +3-5 % from L2 reuse of the weight panels,
+  // tools/bench_pp_prio.py with TW_GEMM_GROUP_M); plain row-major elsewhere (K = 5120 and the
+  // decoder's M = B x 447 shapes lose with grouping: round 4, profiles/r04_b_l2_epilogue_study.txt)
+  pl.group_m = (kmajor && batch == 1 && M >= 65536 && K <= 2048) ? 8 : 1;
+  if ((flags >> F_GROUP_M_SHIFT) & 15) pl.group_m = (flags >> F_GROUP_M_SHIFT) & 15;   // forced (tools/bench_group.py)
+  pl.epi = pick_epilogue(p, batch);
+  // 256x256 tiles (8 waves) when the problem has enough tiles to fill the chip, else 128x128
+  const int64_t t256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256) * batch;
+  const int64_t t128 = (int64_t)((M + 127) / 128) * ((N + 127) / 128);
+  // measured crossovers (tools/bench_gemm.py, r01, specialised epilogues): the persistent 256x256
+  // ping-pong kernel wins every large K-major/K-major shape (1.05-1.27 PFLOP/s); the 2-stage
+  // 256x256 tile the large transposed ones; 128x128 the small grids (< ~1000 256-tiles).  The
+  // 256x128 rings are kept as forced variants only.
+  Route tile = (t256 >= 1000 && K >= 256) ? Route::T256 : Route::T128;
+  // very long K (the LM-head input gradient, K = 51 904): the persistent kernel wins from one round up
+  // (3356 vs 4006 us on 560 tiles, tools/bench_head_bwd.py), its per-tile fixed cost being amortised
+  if (kmajor && K >= 8192 && t256 >= G) tile = Route::T256;
+  // ... and its transposed-B form (the student's LM-head dX = dlogits . E, K = 51 904, 560 tiles) on the 2-stage
+  // 256x256 tile: 4059 vs 4370 us on the 128x128 one (tools/bench_gemm.py "dX head", profiles/r06_a_gemm.log)
+  if (!a_trans && b_trans && K >= 8192 && t256 >= G / 2) tile = Route::T256;   // c2's: 168 tiles, 1297 vs 1643 us
+  // K-major forward grids of 1-4 rounds whose rounds are well filled (c2's B = 32 shapes: the teacher encoder's
+  // N = 1280 Linears at M = 48 000, 940 256-tiles = 3.67 rounds, 92 % of the workgroup-rounds busy; the student
+  // decoder's fused QKV and fc1): the persistent kernel.  Grids with a mostly idle last round take the whole-round
+  // + 128x128 tail split below (dp_tail_plan).  Fill threshold 85 % (c2 +0.6 %, c3 unchanged: same box, round 4)
+  // (K >= 1024: at c2's student decoder K = 768 -- 12 K-tiles per tile -- the 128x128 kernel wins: fused QKV 69 vs
+  // 85 us, fc1 90 vs 105 us, profiles/r06_l_gemm_c2.log)
+  if (kmajor && tile == Route::T128 && K >= 1024 && t256 >= G && t256 * 100 >= ((t256 + G - 1) / G) * G * 85)
+    tile = Route::T256;
+  if (tile == Route::T256 && kmajor) tile = Route::Persistent;
+  if (flags & F_TILE128) tile = Route::T128;        // forced tile (benchmarking / A-B comparisons)
+  if (flags & F_TILE256) tile = Route::T256;
+  if (flags & F_TILE256x128) tile = Route::T256x128S3;
+  if (flags & F_TILE256PP) tile = kmajor ? Route::Persistent : Route::T128;   // (K-major A and B only)
+  // the fp16 persistent kernel is compiled with the fast full-tile epilogues only (gemm_impl.h epilogue_k): a grid
+  // ragged in M or N runs its whole 256x256 tiles there and the edge strips on the 128x128 kernel
+  // (launch_pp_edges); K tails, batches, row-periodic residuals and the generic epilogue kind take the 128x128 kernel
+  if (H && tile == Route::Persistent && ((M % 256) || (N % 256))) {
+    const bool edges = (K % BK) == 0 && pl.epi != EPI_GENERIC && batch == 1 && p.res_mod == 0 && M >= 256 && N >= 256;
+    tile = edges ? Route::PersistentEdges : Route::T128;
+  }
+  if (H && tile == Route::Persistent && ((K % BK) || pl.epi == EPI_GENERIC)) tile = Route::T128;
+  pl.tiles = (tile == Route::T256 || tile == Route::Persistent || tile == Route::PersistentEdges) ? t256 / batch : t128;
+  // decode-step GEMMs (tools/bench_skinny.py, r01): the weight-streaming kernel wins for N <= 3840
+  // (and N <= 8192 at M <= 64); the LM head and wide M=128 GEMMs stream faster as 128x128 tiles
+  // (row-blocked skinny launches above 128 rows measured slower at M = 512, tools/bench_decode_gemm.py: qkv 50 vs
+  // 21 us, fc2 69 vs 60 us against the 128x128 tiles)
+  if (kmajor && batch == 1 && M <= 128 && (N <= 4096 || (M <= 64 && N <= 8192)) && !(flags & F_FORCED_TILE)) {
+    // decode-step GEMMs: stream W once.  With fewer than 512 workgroups and M > 32 the K range is
+    // also split over workgroups (chunks of >= 4 k-steps) into fp32 partials, reduced with the
+    // epilogue (c4 batch 64 / 128: -3 / -4 % per step; at batch 1 the extra launch loses 9 %).
+    const int nwg = (N + 15) / 16 * skinny_row_blocks(M), nk = (K + 31) / 32;
+    int S = std::min((512 + nwg - 1) / nwg, nk / 4);
+    if ((flags & F_NOSPLIT) || M <= 32) S = 1;        // small batches: the reduce launch costs more than it saves
+    if (S < 1 || !have_ws) S = 1;
+    pl.route = S > 1 ? Route::SkinnySplitK : Route::Skinny;
+    pl.S = S;
+    return pl;
+  }
+  if (have_ws && !(flags & (F_NOSPLIT | F_FORCED_TILE))) {   // dW split-K, partials of at most 1 GiB
+    const int S = splitk_factor(p, batch, a_trans, b_trans, G, &pl.split_tile);
+    if (S > 0 && (size_t)S * M * N * sizeof(float) <= ((size_t)1 << 30)) {
+      pl.route = Route::SplitKDw;
+      pl.S = S;
+      return pl;
+    }
+    pl.split_tile = 0;
+  }
+  if (flags & F_TILE256x128_S2) tile = Route::T256x128S2;
+  // mid-sized forward grids (1-4 rounds of 256-tiles): whole rounds persistent + a split-K tail
+  // (tools/bench_gemm_dec.py: fc2 K = 5120 417 -> 347 us; at K = 1280 the split's fp32 round trip costs
+  // more than the third round it saves, 125 -> 140 us, so short K stays on the 128x128 kernel; grids of less than
+  // one round, the 512-clip decode step's Linears, follow the same K >= 3072 rule)
+  if (have_ws && kmajor && tile == Route::T128 && K >= 3072 && !(flags & F_NO_PLAN)) {
+    int m_dp = 0;
+    const int S = sk_tail_plan(p, batch, (int)G, m_dp);
+    // (fp16: the persistent kernel runs full tiles only, so both parts must be whole 256-row blocks)
+    const bool full = !H || ((N % 256) == 0 && ((M - m_dp * 256) % 256) == 0 && pl.epi != EPI_GENERIC);
+    if (S > 0 && full) {
+      pl.route = Route::RoundsSkTail;
+      pl.S = S;
+      pl.m_dp = m_dp;
+      return pl;
+    }
+  }
+  // whole rounds persistent + a 128x128 tail (dp_tail_plan)
+  if (kmajor && !(flags & F_NO_PLAN)) {
+    int m_dp = 0;
+    // (fp16: the persistent part must be whole 256x256 tiles with a fast epilogue)
+    if (dp_tail_plan(p, batch, (int)G, m_dp) && (!H || ((N % 256) == 0 && (K % BK) == 0 && pl.epi != EPI_GENERIC))) {
+      pl.route = Route::RoundsDpTail;
+      pl.m_dp = m_dp;
+      return pl;
+    }
+  }
+  // Grids of at most one 128x128 tile per CU (the 512-clip decode step's Linears: 40-160 tiles, one workgroup per
+  // CU anyway) run on a 4-stage ring: three K-steps in flight instead of one hide the load latency that bounds a
+  // 20-K-step tile.  Same tile, same K order: bit-identical.  c4 fp16 155.8 -> 158.5 utt/s, c5 16.93 -> 17.09
+  // audio s/s (same box, profiles/r03_s_gemm_deep_ab.log).  F_TILE128 keeps the 2-stage kernel.
+  if (tile == Route::T128 && kmajor && !(flags & F_TILE128) && t128 * batch <= G) tile = Route::T128Ring4;
+  // fp16 training's dX / dW products: the 2-stage 256x256 and 128x128 tiles only (the 256x128 rings are forced
+  // A/B variants of the bf16 kernels; not instantiating them for fp16 keeps the library's build time down)
+  if (H && !kmajor && tile != Route::T256) tile = Route::T128;
+  pl.route = tile;
+  return pl;
+}
+
+// Rows [m0, m0 + M) x columns [n0, n0 + N) of a K-major, unbatched product as a product of its own: every operand
+// and epilogue pointer advanced, the epilogue kind picked again (the alignment may have changed).
+GemmP sub_problem(const GemmP& p, int m0, int n0, int M, int N) {
+  const int csz = p.c_dtype == TW_BF16 ? 2 : 4, rsz = p.res_dtype == TW_BF16 ? 2 : 4;
+  GemmP q = p;
+  q.A = p.A + (int64_t)m0 * p.lda;
+  q.B = p.B + (int64_t)n0 * p.ldb;
+  q.C = (char*)p.C + ((int64_t)m0 * p.ldc + n0) * csz;
+  if (p.bias) q.bias = p.bias + n0;
+  if (p.res) q.res = (const char*)p.res + ((int64_t)m0 * p.ldr + n0) * rsz;
+  if (p.aux) q.aux = p.aux + (int64_t)m0 * p.ldaux + n0;
+  q.M = M;
+  q.N = N;
+  q.epi = pick_epilogue(q, 1);
+  return q;
+}
+
+// S chunks of the K range as S batch entries into the fp32 partials `ws` [S][M][N], no epilogue; chunk s starts
+// sA / sB elements into A / B
+GemmP chunked(const GemmP& p, int S, int64_t sA, int64_t sB, float* ws) {
+  GemmP q = p;
+  q.K = p.K / S;
+  q.sA = sA; q.sB = sB;
+  q.C = ws; q.ldc = p.N; q.sC = (int64_t)p.M * p.N; q.c_dtype = TW_F32;
+  q.alpha = 1.f; q.flags = 0; q.bias = nullptr; q.res = nullptr; q.aux = nullptr; q.ws = nullptr;
+  q.epi = pick_epilogue(q, S);
+  return q;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Split-K for weight gradients (splitk_factor): the chunks on the 128x128 or the 256x256 kernel, then
+// splitk_reduce_kernel
+// ---------------------------------------------------------------------------------------------
+template <bool H>
+int launch_splitk_dw(const GemmP& p, int S, int split_tile, float* ws, hipStream_t stream) {
+  const int Kc = p.K / S;
+  const GemmP q = chunked(p, S, (int64_t)Kc * p.lda, (int64_t)Kc * p.ldb, ws);   // A is [K][M] (lda), B is [K][N] (ldb)
+  if (split_tile == 256) launch<H, true, true, 256, 256, 2, 4, 2>(q, S, stream);
+  else launch<H, true, true, 128, 128, 2, 2, 2>(q, S, stream);
+  TW_CHECK_LAUNCH();
+  const int64_t work = (int64_t)p.M * (p.N / 4);
+  const int grid = (int)std::min<int64_t>((work + 255) / 256, 4096);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, (const float*)ws, S,
+                     (int64_t)p.M * p.N, (float*)p.C, p.ldc, p.M, p.N, p.alpha, (p.flags & F_ROUND) ? (H ? 2 : 1) : 0,
+                     (p.flags & F_ACCUM) ? 1 : 0);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+template <bool H>
+int launch_skinny_route(GemmP p, int S, float* ws, hipStream_t stream) {
+  p.ws = ws;                                           // (nullptr, S = 1: the epilogue in the kernel)
+  launch_skinny<H>(p, stream, S);
+  if (ws) {
+    TW_CHECK_LAUNCH();
+    const int64_t total = (int64_t)p.M * p.N;
+    hipLaunchKernelGGL(skinny_reduce_kernel<H>, dim3((int)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0,
+                       stream, p, S);
+  }
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+// whole rounds on the persistent kernel, the remaining rows as S split-K chunks (sk_tail_plan)
+template <bool H>
+int launch_sk_tail(const GemmP& p, int S, int m_dp, float* ws, hipStream_t stream) {
+  const int r0 = m_dp * 256;
+  if (m_dp > 0) {
+    launch_pp<H>(sub_problem(p, 0, 0, r0, p.N), 1, stream);                  // whole rounds: the unsplit kernel
+    TW_CHECK_LAUNCH();
+  }
+  GemmP r = sub_problem(p, r0, 0, p.M - r0, p.N);      // tail rows: S K-chunks -> fp32 partials
+  GemmP q = chunked(r, S, p.K / S, p.K / S, ws);       // chunk s starts at column s*K/S of A and B
+  q.group_m = 1;
+  launch_pp<H>(q, S, stream);
+  TW_CHECK_LAUNCH();
+  r.ws = ws;                                           // ordered chunk sum + the full epilogue
+  const int64_t work = (int64_t)r.M * (p.N / 4);
+  hipLaunchKernelGGL(sk_reduce_kernel<H>, dim3((int)std::min<int64_t>((work + 255) / 256, 4096)), dim3(256), 0,
+                     stream, r, S);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+// whole rounds on the persistent kernel, the remaining rows as 128x128 tiles on the 4-stage ring (dp_tail_plan)
 template <bool H>
 int launch_dp_tail(const GemmP& p, int m_dp, hipStream_t stream) {
-  GemmP d = p;                                           // whole rounds: the persistent kernel
-  d.M = m_dp * 256;
-  launch_pp<H>(d, 1, stream);
+  const int r0 = m_dp * 256;
+  launch_pp<H>(sub_problem(p, 0, 0, r0, p.N), 1, stream);
   TW_CHECK_LAUNCH();
-  GemmP q = p;                                           // the remaining rows: 128x128 tiles, 4-stage ring
-  const int64_t r0 = (int64_t)m_dp * 256;
-  const int csz = p.c_dtype == TW_BF16 ? 2 : 4;
-  q.A = p.A + r0 * p.lda;
-  q.M = p.M - (int)r0;
-  q.C = (char*)p.C + r0 * p.ldc * csz;
-  if (p.res) q.res = (const char*)p.res + r0 * p.ldr * (p.res_dtype == TW_BF16 ? 2 : 4);
-  if (p.aux) q.aux = p.aux + r0 * p.ldaux;
-  q.epi = pick_epilogue(q, 1);
-  launch<H, false, false, 128, 128, 2, 2, 4>(q, 1, stream);
+  launch<H, false, false, 128, 128, 2, 2, 4>(sub_problem(p, r0, 0, p.M - r0, p.N), 1, stream);
   TW_CHECK_LAUNCH();
-  return 1;
+  return TW_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -951,50 +1091,43 @@ int launch_dp_tail(const GemmP& p, int m_dp, hipStream_t stream) {
 template <bool H>
 int launch_pp_edges(const GemmP& p, hipStream_t stream) {
   const int Mf = p.M / 256 * 256, Nf = p.N / 256 * 256;
-  const int csz = p.c_dtype == TW_BF16 ? 2 : 4, rsz = p.res_dtype == TW_BF16 ? 2 : 4;
-  auto sub = [&](int m0, int n0, int M, int N) {
-    GemmP q = p;
-    q.A = p.A + (int64_t)m0 * p.lda;
-    q.B = p.B + (int64_t)n0 * p.ldb;
-    q.C = (char*)p.C + ((int64_t)m0 * p.ldc + n0) * csz;
-    if (p.bias) q.bias = p.bias + n0;
-    if (p.res) q.res = (const char*)p.res + ((int64_t)m0 * p.ldr + n0) * rsz;
-    if (p.aux) q.aux = p.aux + (int64_t)m0 * p.ldaux + n0;
-    q.M = M;
-    q.N = N;
-    q.epi = pick_epilogue(q, 1);
-    return q;
-  };
-  launch_pp<H>(sub(0, 0, Mf, Nf), 1, stream);
+  launch_pp<H>(sub_problem(p, 0, 0, Mf, Nf), 1, stream);
   TW_CHECK_LAUNCH();
   if (Nf < p.N) {
-    launch<H, false, false, 128, 128, 2, 2, 2>(sub(0, Nf, p.M, p.N - Nf), 1, stream);
+    launch<H, false, false, 128, 128, 2, 2, 2>(sub_problem(p, 0, Nf, p.M, p.N - Nf), 1, stream);
     TW_CHECK_LAUNCH();
   }
   if (Mf < p.M) {
-    launch<H, false, false, 128, 128, 2, 2, 2>(sub(Mf, 0, p.M - Mf, Nf), 1, stream);
+    launch<H, false, false, 128, 128, 2, 2, 2>(sub_problem(p, Mf, 0, p.M - Mf, Nf), 1, stream);
     TW_CHECK_LAUNCH();
   }
   return TW_OK;
 }
 
-}  // namespace
+// one kernel over the whole product (plan_gemm hands a layout only the routes instantiated for it)
+template <bool H, bool AT, bool BT>
+void dispatch(const GemmP& p, int batch, hipStream_t stream, Route route) {
+  constexpr bool KMAJOR = !AT && !BT;
+  constexpr bool RINGS = !H || KMAJOR;
+  switch (route) {
+    case Route::Persistent: if constexpr (KMAJOR) launch_pp<H>(p, batch, stream); break;
+    case Route::T128Ring4: if constexpr (KMAJOR) launch<H, AT, BT, 128, 128, 2, 2, 4>(p, batch, stream); break;
+    case Route::T256: launch<H, AT, BT, 256, 256, 2, 4, 2>(p, batch, stream); break;
+    case Route::T256x128S3: if constexpr (RINGS) launch<H, AT, BT, 256, 128, 4, 2, 3>(p, batch, stream); break;
+    case Route::T256x128S2: if constexpr (RINGS) launch<H, AT, BT, 256, 128, 4, 2, 2>(p, batch, stream); break;
+    default: launch<H, AT, BT, 128, 128, 2, 2, 2>(p, batch, stream); break;
+  }
+}
 
-// the same per-device block for other stream-ordered scratch users (decode attention split partials)
-#ifndef TW_GEMM_TU_F16
-void* tw_device_workspace(hipStream_t stream, size_t bytes) { return splitk_workspace(stream, bytes); }
-#endif
-
-namespace {
-
-// H = false: tw_gemm_bf16; H = true: tw_gemm_f16 (the fp16 model's forward products, and since round 6 the
-// transposed dX / dW products of fp16-autocast training: the same kernels instantiated for fp16 words)
-template <bool H>
-int gemm_run(const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb, int b_trans, void* C, int64_t ldc,
-             int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB, int64_t sC, float alpha,
-             const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype, int res_mod, void* aux,
-             int64_t ldaux, int64_t sAux, int flags, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || batch <= 0) return TW_OK;
+// Validation of a tw_gemm_bf16 (H = false) / tw_gemm_f16 (H = true) call and its parameter block; GEMM_EMPTY:
+// nothing to compute.  (The fp16 entries serve the fp16 model's forward products and, since round 6, the
+// transposed dX / dW products of fp16-autocast training: the same kernels instantiated for fp16 words.)
+constexpr int GEMM_EMPTY = -1;
+int gemm_setup(bool H, const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb, int b_trans, void* C,
+               int64_t ldc, int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB, int64_t sC, float alpha,
+               const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype, int res_mod, void* aux,
+               int64_t ldaux, int64_t sAux, int flags, GemmP& p) {
+  if (M <= 0 || N <= 0 || batch <= 0) return GEMM_EMPTY;
   if (H) {
     if ((c_dtype != TW_F32 && c_dtype != TW_F16) || ((flags & F_RES) && res_dtype != TW_F32 && res_dtype != TW_F16))
       return TW_EUNSUPPORTED;
@@ -1015,148 +1148,49 @@ int gemm_run(const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb
   if ((flags & (F_AUX_OUT | F_DGELU)) && !aux) return TW_EINVAL;
   if (c_dtype != TW_F32 && c_dtype != TW_BF16) return TW_EUNSUPPORTED;
   if (res_dtype != TW_F32 && res_dtype != TW_BF16) res_dtype = TW_F32;   // unused without F_RES
-  GemmP p;
   p.A = (const bf16*)A; p.B = (const bf16*)B; p.C = C;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.sA = sA; p.sB = sB; p.sC = sC; p.alpha = alpha; p.bias = (const bf16*)bias;
   p.res = res; p.ldr = ldr; p.sR = sR; p.res_dtype = res_dtype; p.res_mod = res_mod;
   p.aux = (bf16*)aux; p.ldaux = ldaux; p.sAux = sAux; p.c_dtype = c_dtype; p.flags = flags;
   p.ws = nullptr;
-  // tile order: runs of 8 m-tiles walked n-tile by n-tile for the tall, short-K forward GEMMs (the
-  // encoder's M = B x 1500 projections: +3-5 % from L2 reuse of the weight panels,
-  // tools/bench_pp_prio.py with TW_GEMM_GROUP_M); plain row-major elsewhere (K = 5120 and the
-  // decoder's M = B x 447 shapes lose with grouping: round 4, profiles/r04_b_l2_epilogue_study.txt)
-  const bool grouped = !a_trans && !b_trans && batch == 1 && M >= 65536 && K <= 2048;
-  p.group_m = grouped ? 8 : 1;
-  if ((flags >> 24) & 15) p.group_m = (flags >> 24) & 15;     // forced tile order (A/B runs: tools/bench_group.py)
-  p.epi = pick_epilogue(p, batch);
-  // 256x256 tiles (8 waves) when the problem has enough tiles to fill the chip, else 128x128
-  const int64_t t256 = (int64_t)((M + 255) / 256) * ((N + 255) / 256) * batch;
-  // measured crossovers (tools/bench_gemm.py, r01, specialised epilogues): the persistent 256x256
-  // ping-pong kernel wins every large K-major/K-major shape (1.05-1.27 PFLOP/s); the 2-stage
-  // 256x256 tile the large transposed ones; 128x128 the small grids (< ~1000 256-tiles).  The
-  // 256x128 3-stage ring is kept as a forced variant only.
-  int tile = (t256 >= 1000 && K >= 256) ? 256 : 128;
-  // very long K (the LM-head input gradient, K = 51 904): the persistent kernel wins from one round up
-  // (3356 vs 4006 us on 560 tiles, tools/bench_head_bwd.py), its per-tile fixed cost being amortised
-  if (!a_trans && !b_trans && K >= 8192 && t256 >= pp_grid_cus()) tile = 256;
-  // ... and its transposed-B form (the student's LM-head dX = dlogits . E, K = 51 904, 560 tiles) on the 2-stage
-  // 256x256 tile: 4059 vs 4370 us on the 128x128 one (tools/bench_gemm.py "dX head", profiles/r06_a_gemm.log)
-  if (!a_trans && b_trans && K >= 8192 && t256 >= pp_grid_cus() / 2) tile = 256;   // c2's: 168 tiles, 1297 vs 1643 us
-  // K-major forward grids of 1-4 rounds whose rounds are well filled (c2's B = 32 shapes: the teacher encoder's
-  // N = 1280 Linears at M = 48 000, 940 256-tiles = 3.67 rounds, 92 % of the workgroup-rounds busy; the student
-  // decoder's fused QKV and fc1): the persistent kernel.  Grids with a mostly idle last round take the whole-round
-  // + 128x128 tail split below (dp_tail_plan).  Fill threshold 85 % (c2 +0.6 %, c3 unchanged: same box, round 4)
-  // (K >= 1024: at c2's student decoder K = 768 -- 12 K-tiles per tile -- the 128x128 kernel wins: fused QKV 69 vs
-  // 85 us, fc1 90 vs 105 us, profiles/r06_l_gemm_c2.log)
-  if (!a_trans && !b_trans && tile == 128 && K >= 1024) {
-    const int64_t G = pp_grid_cus();
-    if (t256 >= G && t256 * 100 >= ((t256 + G - 1) / G) * G * 85) tile = 256;
+  return TW_OK;
+}
+
+// validate and fill GemmP, plan, launch the plan
+template <bool H>
+int gemm_run(const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb, int b_trans, void* C, int64_t ldc,
+             int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB, int64_t sC, float alpha,
+             const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype, int res_mod, void* aux,
+             int64_t ldaux, int64_t sAux, int flags, hipStream_t stream) {
+  GemmP p;
+  const int rc = gemm_setup(H, A, lda, a_trans, B, ldb, b_trans, C, ldc, c_dtype, M, N, K, batch, sA, sB, sC, alpha, bias,
+                            res, ldr, sR, res_dtype, res_mod, aux, ldaux, sAux, flags, p);
+  if (rc != TW_OK) return rc == GEMM_EMPTY ? TW_OK : rc;
+  const int cus = device_cus();
+  GemmPlan pl = plan_gemm(p, batch, a_trans, b_trans, H, cus, true);
+  if (!plan_fits(pl, batch)) return TW_EINVAL;
+  float* ws = nullptr;
+  if (const size_t bytes = plan_ws_bytes(pl, p)) {
+    ws = (float*)splitk_workspace(stream, bytes);
+    // no block (inside a stream capture when it would have to grow): the plan without a workspace
+    if (!ws) pl = plan_gemm(p, batch, a_trans, b_trans, H, cus, false);
   }
-  if (tile == 256 && !a_trans && !b_trans) tile = 2562;
-  if (flags & 256) tile = 128;        // forced tile (benchmarking / A-B comparisons)
-  if (flags & 512) tile = 256;
-  if (flags & 1024) tile = 2561;      // 256x128, 3-stage ring
-  if (flags & 2048) tile = 2562;      // 256x256 ping-pong (K-major A and B only)
-  // the fp16 persistent kernel is compiled with the fast full-tile epilogues only (gemm_impl.h epilogue_k): a grid
-  // ragged in M or N runs its whole 256x256 tiles there and the edge strips on the 128x128 kernel (tile 2564,
-  // launch_pp_edges); K tails, batches, row-periodic residuals and the generic epilogue kind take the 128x128 kernel
-  if (H && tile == 2562 && ((M % 256) || (N % 256))) {
-    const bool edges = (K % BK) == 0 && p.epi != EPI_GENERIC && batch == 1 && res_mod == 0 && M >= 256 && N >= 256;
-    tile = edges ? 2564 : 128;
+  p.group_m = pl.group_m;
+  p.epi = pl.epi;
+  switch (pl.route) {
+    case Route::Skinny:
+    case Route::SkinnySplitK: return launch_skinny_route<H>(p, pl.S, ws, stream);
+    case Route::SplitKDw: return launch_splitk_dw<H>(p, pl.S, pl.split_tile, ws, stream);
+    case Route::RoundsSkTail: return launch_sk_tail<H>(p, pl.S, pl.m_dp, ws, stream);
+    case Route::RoundsDpTail: return launch_dp_tail<H>(p, pl.m_dp, stream);
+    case Route::PersistentEdges: return launch_pp_edges<H>(p, stream);
+    default: break;
   }
-  if (H && tile == 2562 && ((K % BK) || p.epi == EPI_GENERIC)) tile = 128;
-  const int64_t ntiles = (tile == 256 || tile == 2562 || tile == 2564) ? t256 / batch
-                                                                       : (int64_t)((M + 127) / 128) * ((N + 127) / 128);
-  if (ntiles > 0x7fffffff || ntiles * batch > 0x7fffffff || batch > 65535) return TW_EINVAL;
-  // decode-step GEMMs (tools/bench_skinny.py, r01): the weight-streaming kernel wins for N <= 3840
-  // (and N <= 8192 at M <= 64); the LM head and wide M=128 GEMMs stream faster as 128x128 tiles
-  // (row-blocked skinny launches above 128 rows measured slower at M = 512, tools/bench_decode_gemm.py: qkv 50 vs
-  // 21 us, fc2 69 vs 60 us against the 128x128 tiles)
-  const bool skinny = !a_trans && !b_trans && batch == 1 && M <= 128 && (N <= 4096 || (M <= 64 && N <= 8192)) &&
-                      !(flags & (256 | 512 | 1024 | 2048));
-  if (skinny && ((uintptr_t)A & 15) == 0) {
-    // decode-step GEMMs: stream W once.  With fewer than 512 workgroups and M > 32 the K range is
-    // also split over workgroups (chunks of >= 4 k-steps) into fp32 partials, reduced with the
-    // epilogue (c4 batch 64 / 128: -3 / -4 % per step; at batch 1 the extra launch loses 9 %).
-    p.ws = nullptr;
-    const int nwg = (N + 15) / 16 * skinny_row_blocks(M), nk = (K + 31) / 32;
-    int S = std::min((512 + nwg - 1) / nwg, nk / 4);
-    if ((flags & 16384) || M <= 32) S = 1;          // small batches: the reduce launch costs more than it saves
-    void* ws = S > 1 ? splitk_workspace(stream, (size_t)S * M * N * sizeof(float)) : nullptr;
-    if (ws) {
-      p.ws = (float*)ws;
-      launch_skinny<H>(p, stream, S);
-      TW_CHECK_LAUNCH();
-      const int64_t total = (int64_t)M * N;
-      hipLaunchKernelGGL(skinny_reduce_kernel<H>, dim3((int)std::min<int64_t>((total + 255) / 256, 2048)), dim3(256), 0,
-                         stream, p, S);
-    } else {
-      launch_skinny<H>(p, stream);
-    }
-    TW_CHECK_LAUNCH();
-    return TW_OK;
-  }
-  if (!(flags & (16384 | 256 | 512 | 1024 | 2048))) {   // 16384: no split-K; forced tiles: A/B runs
-    int sk_tile = 128;
-    const int S = splitk_factor(p, batch, a_trans, b_trans, &sk_tile);
-    const size_t bytes = (size_t)S * M * N * sizeof(float);
-    void* ws = (S > 0 && bytes <= ((size_t)1 << 30)) ? splitk_workspace(stream, bytes) : nullptr;
-    if (ws) {
-      GemmP q = p;
-      const int Kc = K / S;
-      q.K = Kc;
-      q.sA = (int64_t)Kc * lda;                      // A is [K][M] (lda), B is [K][N] (ldb)
-      q.sB = (int64_t)Kc * ldb;
-      q.C = ws; q.ldc = N; q.sC = (int64_t)M * N; q.c_dtype = TW_F32;
-      q.alpha = 1.f; q.flags = 0; q.bias = nullptr; q.res = nullptr; q.aux = nullptr;
-      q.epi = pick_epilogue(q, S);
-      if (sk_tile == 256) launch<H, true, true, 256, 256, 2, 4, 2>(q, S, stream);
-      else launch<H, true, true, 128, 128, 2, 2, 2>(q, S, stream);
-      TW_CHECK_LAUNCH();
-      const int64_t work = (int64_t)M * (N / 4);
-      const int grid = (int)std::min<int64_t>((work + 255) / 256, 4096);
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, stream, (const float*)ws, S,
-                         (int64_t)M * N, (float*)C, ldc, M, N, alpha, (flags & F_ROUND) ? (H ? 2 : 1) : 0,
-                         (flags & F_ACCUM) ? 1 : 0);
-      TW_CHECK_LAUNCH();
-      return TW_OK;
-    }
-  }
-  // mid-sized forward grids (1-4 rounds of 256-tiles): whole rounds persistent + a split-K tail
-  // (flag 262144 forces the 256x128 2-stage tile)
-  if (flags & 262144) tile = 2563;
-  // (tools/bench_gemm_dec.py: fc2 K = 5120 417 -> 347 us; at K = 1280 the split's fp32 round trip costs
-  // more than the third round it saves, 125 -> 140 us, so short K stays on the 128x128 kernel; grids of less than
-  // one round, the 512-clip decode step's Linears, follow the same K >= 3072 rule)
-  if (!a_trans && !b_trans && tile == 128 && K >= 3072 &&
-      !(flags & (16384 | 256 | 512 | 1024 | 2048 | 262144))) {
-    int m_dp = 0;
-    const int S = sk_tail_plan(p, batch, m_dp);
-    // (fp16: the persistent kernel runs full tiles only, so both parts must be whole 256-row blocks)
-    const bool full = !H || ((N % 256) == 0 && ((M - m_dp * 256) % 256) == 0 && p.epi != EPI_GENERIC);
-    if (S > 0 && full && launch_sk_tail<H>(p, S, m_dp, stream)) return TW_OK;
-  }
-  // whole rounds persistent + a 128x128 tail (dp_tail_plan)
-  if (!a_trans && !b_trans && !(flags & (16384 | 256 | 512 | 1024 | 2048 | 262144))) {
-    int m_dp = 0;
-    // (fp16: the persistent part must be whole 256x256 tiles with a fast epilogue)
-    if (dp_tail_plan(p, batch, m_dp) && (!H || ((N % 256) == 0 && (K % BK) == 0 && p.epi != EPI_GENERIC)) &&
-        launch_dp_tail<H>(p, m_dp, stream))
-      return TW_OK;
-  }
-  // Grids of at most one 128x128 tile per CU (the 512-clip decode step's Linears: 40-160 tiles, one workgroup per
-  // CU anyway) run on a 4-stage ring: three K-steps in flight instead of one hide the load latency that bounds a
-  // 20-K-step tile.  Same tile, same K order: bit-identical.  c4 fp16 155.8 -> 158.5 utt/s, c5 16.93 -> 17.09
-  // audio s/s (same box, profiles/r03_s_gemm_deep_ab.log).  Flag 256 (forced 128x128) keeps the 2-stage kernel.
-  if (tile == 128 && !a_trans && !b_trans && !(flags & 256) &&
-      (int64_t)((M + 127) / 128) * ((N + 127) / 128) * batch <= pp_grid_cus())
-    tile = 1284;
-  if (tile == 2564) return launch_pp_edges<H>(p, stream);
-  if (!a_trans && !b_trans) dispatch<H, false, false>(p, batch, stream, tile);
-  else if (!a_trans && b_trans) dispatch<H, false, true>(p, batch, stream, tile);
-  else if (a_trans && !b_trans) dispatch<H, true, false>(p, batch, stream, tile);
-  else dispatch<H, true, true>(p, batch, stream, tile);
+  if (!a_trans && !b_trans) dispatch<H, false, false>(p, batch, stream, pl.route);
+  else if (!a_trans && b_trans) dispatch<H, false, true>(p, batch, stream, pl.route);
+  else if (a_trans && !b_trans) dispatch<H, true, false>(p, batch, stream, pl.route);
+  else dispatch<H, true, true>(p, batch, stream, pl.route);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
@@ -1237,6 +1271,23 @@ extern "C" int tw_gemm_bf16(const void* A, int64_t lda, int a_trans, const void*
                             void* aux, int64_t ldaux, int64_t sAux, int flags, hipStream_t stream) {
   return gemm_run<false>(A, lda, a_trans, B, ldb, b_trans, C, ldc, c_dtype, M, N, K, batch, sA, sB, sC, alpha, bias,
                          res, ldr, sR, res_dtype, res_mod, aux, ldaux, sAux, flags, stream);
+}
+
+extern "C" int tw_gemm_route(const void* A, int64_t lda, int a_trans, const void* B, int64_t ldb, int b_trans, void* C,
+                             int64_t ldc, int c_dtype, int M, int N, int K, int batch, int64_t sA, int64_t sB,
+                             int64_t sC, const void* bias, const void* res, int64_t ldr, int64_t sR, int res_dtype,
+                             int res_mod, void* aux, int64_t ldaux, int64_t sAux, int flags, int is_f16, int cus,
+                             int have_ws, int* out) {
+  GemmP p;
+  const int rc = gemm_setup(is_f16 != 0, A, lda, a_trans, B, ldb, b_trans, C, ldc, c_dtype, M, N, K, batch, sA, sB, sC,
+                            1.f, bias, res, ldr, sR, res_dtype, res_mod, aux, ldaux, sAux, flags, p);
+  for (int i = 0; i < 6; ++i) out[i] = i == 0 ? -1 : 0;
+  if (rc != TW_OK) return rc == GEMM_EMPTY ? TW_OK : rc;
+  const GemmPlan pl = plan_gemm(p, batch, a_trans, b_trans, is_f16 != 0, cus > 0 ? std::max(cus, 8) : device_cus(),
+                                have_ws != 0);
+  if (!plan_fits(pl, batch)) return TW_EINVAL;
+  out[0] = (int)pl.route; out[1] = pl.S; out[2] = pl.m_dp; out[3] = pl.split_tile; out[4] = pl.group_m; out[5] = pl.epi;
+  return TW_OK;
 }
 
 extern "C" int tw_gemv_bf16(const void* x, int64_t ldx, const float* ln_w, const float* ln_b, float eps, const void* W,

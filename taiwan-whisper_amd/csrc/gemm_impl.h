@@ -22,6 +22,26 @@ enum {
   F_AUX_OUT = 32,  // store pre-activation to aux (with F_GELU)
   F_DGELU = 64,    // v = bf16(v * gelu'(aux[m][n]))  (gelu backward, aux = pre-activation)
   F_CLAMP16 = 128, // after the residual add: clamp to +-(fp16 max - 1000) (HF fp16 encoder layer, fp16 GEMMs only)
+  // routing bits (host only; A/B benchmarking and tests): a forced kernel ...
+  F_TILE128 = 256,            // the 128x128 2-stage kernel
+  F_TILE256 = 512,            // the 256x256 2-stage kernel
+  F_TILE256x128 = 1024,       // the 256x128 3-stage ring
+  F_TILE256PP = 2048,         // the persistent 256x256 ping-pong kernel (K-major A and B only)
+  F_TILE256x128_S2 = 262144,  // the 256x128 2-stage ring
+  F_NOSPLIT = 16384,          // ... no split-K (skinny and dW-shaped calls), no whole-rounds + tail split
+  F_GROUP_M_SHIFT = 24,       // bits 24-27: forced tile order, runs of that many m-tiles (0: the default)
+  F_FORCED_TILE = F_TILE128 | F_TILE256 | F_TILE256x128 | F_TILE256PP,   // keeps off the skinny and dW split-K routes
+  F_NO_PLAN = F_FORCED_TILE | F_NOSPLIT | F_TILE256x128_S2,             // keeps off the whole-rounds + tail routes
+  // subtraction diagnostics of the persistent kernel (tools/bench_pp_prio.py, tools/bench_pp_diag.py), wrong results.
+  // These two are tested in the kernel's epilogue in every build (gemm.hip pp_epi_part says why) ...
+  F_DIAG_SKIP_STORES = 4096,        // epilogue arithmetic without the stores
+  F_DIAG_STORE_TILE0 = 1 << 20,     // every tile stored to tile 0 (L2-resident output)
+#ifdef TW_PP_DIAG_VARIANTS
+  // ... these in the diagnostic build only; the default build ignores the bits
+  F_DIAG_TILE_PER_WG = 8192,        // one tile per workgroup instead of the persistent walk
+  F_DIAG_VARIANT_SHIFT = 15,        // bits 15-17: compile-time variant (PP_NO_A1 / PP_NO_RESTAGE / PP_NO_WAIT)
+  F_DIAG_L2_PANELS = 1 << 22,       // every tile stages one block's panels per XCD (L2-resident input)
+#endif
 };
 
 // Inside the kernels a 16-bit C / residual / aux (c_dtype, res_dtype == TW_BF16) holds the operand type of
@@ -108,9 +128,6 @@ __device__ __forceinline__ bf16x8 frag_mn(const char* tile, int cbase, int kk, i
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// Block tile BMxBN, waves WMxWN (each (BM/WM)x(BN/WN)), two LDS stages, one barrier per K-step.
-// blockIdx.x enumerates (m-tile, n-tile) pairs remapped so that consecutive tiles of one m-row
-// share an XCD (L2 reuse of the A panel; blocks b and b+8 share an XCD).
 template <int N>
 __device__ __forceinline__ void wait_vm_lgkm0() {   // s_waitcnt vmcnt(N) lgkmcnt(0), N compile-time
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");

@@ -8,7 +8,8 @@ import torch
 
 from tw import ops
 
-VARIANTS = (("dflt", 0), ("t128", 256), ("t256", 512), ("s3", 1024), ("pp", 2048))   # dflt: the library's own pick
+VARIANTS = (("dflt", 0), ("t128", ops.GEMM_TILE128), ("t256", ops.GEMM_TILE256), ("s3", ops.GEMM_TILE256x128),
+            ("pp", ops.GEMM_TILE256PP))   # dflt: the library's own pick
 SHAPES = [  # (name, M, N, K, a_trans, b_trans)
     ("enc qkv", 96000, 3840, 1280, 0, 0), ("enc out", 96000, 1280, 1280, 0, 0),
     ("enc fc1", 96000, 5120, 1280, 0, 0), ("enc fc2", 96000, 1280, 5120, 0, 0),

@@ -20,7 +20,7 @@ def main():
         A = torch.randn(M, K, device="cuda").bfloat16()
         W = torch.randn(N, K, device="cuda").bfloat16()
         C = torch.empty(M, N, dtype=torch.bfloat16, device="cuda")
-        run = lambda g: ops.gemm(A, W, C, M, N, K, lda=K, ldb=K, ldc=N, flags=ops.GEMM_ROUND | (g << 24))
+        run = lambda g: ops.gemm(A, W, C, M, N, K, lda=K, ldb=K, ldc=N, flags=ops.GEMM_ROUND | ops.GEMM_GROUP_M(g))
         for g in groups:
             run(g)
         ts = {g: [] for g in groups}

@@ -1,5 +1,7 @@
-"""Ping-pong GEMM diagnostics: persistent vs one-tile-per-block, with / without the epilogue
-(debug flag bits 4096 = skip epilogue, 8192 = one tile per workgroup); interleaved rounds."""
+"""Ping-pong GEMM diagnostics: with / without the epilogue's stores (diagnostic flag bits, gemm_impl.h F_DIAG_*:
+4096 = skip the stores, 8192 = one tile per workgroup); interleaved rounds.
+`noepi` is meant for the diagnostic build of the library (make CXXFLAGS+=-DTW_PP_DIAG_VARIANTS); the default build
+ignores 8192 and every main-loop diagnostic bit (gemm.hip pp_epi_part says why 4096 still works there)."""
 import os
 import sys
 

@@ -1,8 +1,8 @@
 """The persistent forward GEMM (gemm_pp_kernel, forced with GEMM_TILE256PP) on the step's K-major shapes with their
 epilogues (bias + round, GELU, bf16 residual): median time and TF/s per shape, and a checksum of each output so that two
 libraries run alternately (tools/calls/ab.sh, TW_HIP_LIB) can be checked for identical bits.  Round 5 used it first
-for the 4-slot ring kernel against the two-buffer one (PP2 = flag 1 << 21 in that build,
-tools/patches/gemm_ring_32k_4slot.patch; profiles/r05_b_*).
+for the 4-slot ring kernel against the two-buffer one (a flag of that build's own selected the ring: historical,
+nothing in the tree reads it; tools/patches/gemm_ring_32k_4slot.patch; profiles/r05_b_*).
 
     python tools/bench_ring.py [rounds] [extra flags]
 """

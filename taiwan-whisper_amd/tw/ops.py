@@ -6,6 +6,9 @@ raises here instead of faulting the GPU.  All launches go on torch's current HIP
 """
 from __future__ import annotations
 
+import collections
+import ctypes
+
 import torch
 
 from ._native import call
@@ -17,6 +20,20 @@ GEMM_CLAMP16 = 128     # fp16 GEMMs: clamp after the residual add (HF fp16 encod
 HALF = (torch.bfloat16, torch.float16)
 GEMM_TILE128, GEMM_TILE256, GEMM_TILE256x128, GEMM_TILE256PP = 256, 512, 1024, 2048   # forced tiles (A/B benchmarking)
 GEMM_NOSPLIT = 16384   # no split-K for dW-shaped calls (A/B benchmarking)
+GEMM_TILE256x128_S2 = 262144   # forced 256x128 tile on the 2-stage ring
+
+
+def GEMM_GROUP_M(g: int) -> int:
+    """Forced tile order: runs of g (1..15) m-tiles walked n-tile by n-tile."""
+    assert 0 < g < 16
+    return g << 24
+
+
+# tw_gemm_route's codes (include/tw_hip.h), in order
+GEMM_ROUTES = ("skinny", "skinny_splitk", "splitk_dw", "rounds_sk_tail", "rounds_dp_tail", "persistent",
+               "persistent_edges", "t128", "t128_ring4", "t256", "t256x128_s3", "t256x128_s2")
+GEMM_EPILOGUES = ("generic", "store_bf16", "store_f32", "gelu", "gelu_aux", "res_bf16", "res_f32", "dgelu")
+GemmRoute = collections.namedtuple("GemmRoute", "route S m_dp split_tile group_m epi")
 
 
 def _dt(t: torch.Tensor) -> int:
@@ -92,6 +109,34 @@ def gemm(A, B, C, M, N, K, *, lda, ldb, ldc, a_trans=False, b_trans=False, alpha
         M, N, K, batch, sA, sB, sC, float(alpha), _ptr(bias), _ptr(res), ldr, sR,
         _dt(res) if res is not None else F32, res_mod, _ptr(aux), ldaux, sAux, flags, _stream()), nbytes)
     return C
+
+
+def gemm_route(A, B, C, M, N, K, *, lda, ldb, ldc, a_trans=False, b_trans=False, bias=None, res=None, ldr=0,
+               res_mod=0, aux=None, ldaux=0, flags=0, batch=1, sA=0, sB=0, sC=0, sR=0, sAux=0, cus=0, have_ws=True):
+    """How gemm() with these arguments runs (tw_gemm_route: the library's validation and planner, nothing launched):
+    GemmRoute(route, S, m_dp, split_tile, group_m, epi) with the route and the epilogue kind as names.
+    A / B / C / bias / res / aux are tensors, or dtypes standing for 16-byte aligned tensors of that type -- nothing
+    is dereferenced, so with cus > 0 (plan for that many CUs) this needs no GPU; cus = 0: the current device's count.
+    have_ws = False: the plan when the split-K workspace cannot be had (a stream capture in which it would grow)."""
+    def arg(t):
+        if t is None:
+            return None, None
+        return (t.data_ptr(), t.dtype) if isinstance(t, torch.Tensor) else (4096, t)
+
+    code = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}
+    (pa, h), (pb, hb), (pc, dc) = arg(A), arg(B), arg(C)
+    assert h in HALF and hb == h, "tw.gemm_route: the bf16 / fp16 GEMMs only"
+    (pbias, _), (pres, dr), (paux, _) = arg(bias), arg(res), arg(aux)
+    if bias is not None:
+        flags |= GEMM_BIAS
+    if res is not None:
+        flags |= GEMM_RES
+    out = (ctypes.c_int * 6)()
+    call("tw_gemm_route", pa, lda, int(a_trans), pb, ldb, int(b_trans), pc, ldc, code[dc], M, N, K, batch, sA, sB, sC,
+         pbias, pres, ldr, sR, code[dr] if res is not None else F32, res_mod, paux, ldaux, sAux, flags,
+         int(h == torch.float16), cus, int(have_ws), out)
+    r = list(out)
+    return GemmRoute(GEMM_ROUTES[r[0]] if r[0] >= 0 else None, r[1], r[2], r[3], r[4], GEMM_EPILOGUES[r[5]])
 
 
 def gemv(x, W, C, *, ln_w=None, ln_b=None, eps=1e-5, bias=None, res=None, aux=None, flags=0, kv=None):

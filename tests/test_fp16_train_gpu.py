@@ -89,12 +89,18 @@ def test_gemm_f16_dx_dgelu_epilogue():
 def test_gemm_f16_ragged_full_tiles_plus_edges_bit_identical(M, N, K, flags):
     """fp16 grids ragged in M or N (the fp16 teacher decoder's M = 64 x 447, the LM head's N = 51 904): the whole
     256x256 tiles on the persistent kernel, the edge strips on the 128x128 kernel -- bit-identical to the 128x128
-    kernel alone (same K order per output)."""
+    kernel alone (same K order per output).  On 256 CUs the first and third shape take that route; the second (560
+    256-tiles, the last round mostly idle) takes whole rounds on the persistent kernel plus a 128x128 tail, and the
+    small fourth the 128x128 tiles on the 4-stage ring."""
     from tw import ops
     g = torch.Generator().manual_seed(M + N + K)
     A = h(torch.randn(M, K, generator=g)).to(DEV)
     W = h(torch.randn(N, K, generator=g) * 0.03).to(DEV)
     bias = h(torch.randn(N, generator=g) * 0.1).to(DEV)
+    n_cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert n_cus == 256, f"the route expectations are written for the MI355X's 256 CUs; this device has {n_cus}"
+    want = {(28608, 5120): ("persistent_edges", 0), (28608, 1280): ("rounds_dp_tail", 102),
+            (28608, 51904): ("persistent_edges", 0), (1000, 2560): ("t128_ring4", 0)}[(M, N)]
     outs = []
     for forced in (0, ops.GEMM_TILE128):
         kw = {}
@@ -108,6 +114,8 @@ def test_gemm_f16_ragged_full_tiles_plus_edges_bit_identical(M, N, K, flags):
         else:
             C = torch.empty(M, N, dtype=torch.float16, device=DEV)
             kw = dict(flags=ops.GEMM_ROUND | forced)
+        r = ops.gemm_route(A, W, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bias, cus=0, **kw)
+        assert (r.route, r.m_dp) == (("t128", 0) if forced else want), r
         ops.gemm(A, W, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bias, **kw)
         torch.cuda.synchronize()
         outs.append((C.clone(), kw.get("aux")))

@@ -30,6 +30,15 @@ def rel_err(a, b):
     return float((a - b).abs().max() / max(b.abs().max().item(), 1e-30))
 
 
+def route_of(*args, **kw):
+    """How ops.gemm(*args, **kw) runs on this device (ops.gemm_route).  The tests named after a route state the route
+    they expect on the MI355X's 256 CUs."""
+    from tw import ops
+    n = torch.cuda.get_device_properties(0).multi_processor_count
+    assert n == 256, f"the route expectations are written for the MI355X's 256 CUs; this device has {n}"
+    return ops.gemm_route(*args, cus=0, **kw)
+
+
 # ----------------------------------------------------------------------------- GEMM
 @pytest.mark.parametrize("a_t,b_t", [(0, 0), (0, 1), (1, 0), (1, 1)])
 @pytest.mark.parametrize("M,N,K", [(200, 136, 72), (128, 128, 64), (257, 520, 1280), (96, 51, 240)])
@@ -256,21 +265,28 @@ def test_gemm_dp_tail_bit_identical(M, N, K):
     A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
     bias, res = torch.randn(N, generator=g), torch.randn(M, N, generator=g)
     Ad, Wd, bd = bf(A).to(DEV), bf(W).to(DEV), bf(bias).to(DEV)
+    m_dp = {28608: 102, 14000: 51}[M]                    # m-tile rows of the whole rounds on 256 CUs
     outs = {}
     for name, f in (("dflt", 0), ("t128", ops.GEMM_TILE128)):
         o = {}
+        want = ("t128", 0) if f else ("rounds_dp_tail", m_dp)
+
+        def gemm(*a, **kw):                              # the route first, then the product
+            r = route_of(*a, **kw)
+            assert (r.route, r.m_dp) == want, (name, r)
+            ops.gemm(*a, **kw)
         Cb = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
-        ops.gemm(Ad, Wd, Cb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, Cb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | f)
         o["bf16"] = Cb
         Cg, aux = torch.empty_like(Cb), torch.empty_like(Cb)
-        ops.gemm(Ad, Wd, Cg, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, aux=aux, ldaux=N,
-                 flags=ops.GEMM_ROUND | ops.GEMM_GELU | ops.GEMM_AUX_OUT | f)
+        gemm(Ad, Wd, Cg, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, aux=aux, ldaux=N,
+             flags=ops.GEMM_ROUND | ops.GEMM_GELU | ops.GEMM_AUX_OUT | f)
         o["gelu"], o["aux"] = Cg, aux
         rb = bf(res).to(DEV)
-        ops.gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
         o["res_bf16"] = rb
         rf = res.clone().to(DEV)
-        ops.gemm(Ad, Wd, rf, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rf, ldr=N, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, rf, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rf, ldr=N, flags=ops.GEMM_ROUND | f)
         o["res_f32"] = rf
         torch.cuda.synchronize()
         outs[name] = o
@@ -290,8 +306,8 @@ def test_gemm_pp_persistent_ragged(M, N, K):
     tiles, the next tile's first K-tiles in flight during the epilogue; at K <= 128 every
     iteration is a tile's last), ragged M and N (masked rows/columns), odd K-tile counts.  Every fast kind (bias+round bf16, bias+round+GELU, in-place bf16 residual) must equal
     the 128x128 kernel bit for bit (same K order) and the fp64 reference within one bf16 ulp.
-    With >= 2 tiles per workgroup (the last two shapes: 561 and 585 tiles) the walk is desynchronised
-    (first tile split around the others, partial sums parked in HBM): still bit-identical."""
+    With more than two rounds of tiles (the last two shapes: 561 and 585 tiles on 256 workgroups) some workgroups walk
+    three tiles and others two, so the tile boundaries of the workgroups drift apart: still bit-identical."""
     from tw import ops
     g = torch.Generator().manual_seed(M * 3 + N + K)
     A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
@@ -331,7 +347,10 @@ def test_gemm_pp_grouped_tile_order():
     """The production tile order of the encoder projections (M >= 65536, K <= 2048: runs of 8 m-tiles
     walked n-tile by n-tile) with a ragged last m-group (ceil(66000 / 256) = 258 m-tiles, 258 % 8 = 2)
     and ragged M: bit-identical to the 128x128 kernel (same K order) for the plain, GELU and in-place
-    residual epilogues, and sampled rows within one bf16 ulp of fp64."""
+    residual epilogues, and sampled rows within one bf16 ulp of fp64.  On 256 CUs the default route of this shape
+    (1290 256-tiles, 10 of them in the last round) is whole rounds on the persistent kernel -- 256 m-tile rows, grouped
+    -- plus a 128x128 tail ("pp"); the forced persistent kernel ("ppf") walks the whole grid, ragged last group
+    included, in the grouped order."""
     from tw import ops
     M, N, K = 66000, 1280, 1280
     g = torch.Generator().manual_seed(5)
@@ -339,21 +358,28 @@ def test_gemm_pp_grouped_tile_order():
     bias = torch.randn(N, generator=g)
     Ad, Wd, bd = bf(A).to(DEV), bf(W).to(DEV), bf(bias).to(DEV)
     res0 = bf(torch.randn(M, N, generator=g)).to(DEV)
+    want = {"t128": ("t128", 0, 8), "pp": ("rounds_dp_tail", 256, 8), "ppf": ("persistent", 0, 8)}
     outs = {}
-    for name, f in (("t128", ops.GEMM_TILE128), ("pp", 0)):
+    for name, f in (("t128", ops.GEMM_TILE128), ("pp", 0), ("ppf", ops.GEMM_TILE256PP)):
         o = {}
+
+        def gemm(*a, **kw):                              # the route first, then the product
+            r = route_of(*a, **kw)
+            assert (r.route, r.m_dp, r.group_m) == want[name], (name, r)
+            ops.gemm(*a, **kw)
         for kind, extra in (("bf16", 0), ("gelu", ops.GEMM_GELU)):
             C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
-            ops.gemm(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | extra | f)
+            gemm(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | extra | f)
             o[kind] = C
         rb = res0.clone()
-        ops.gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
         o["res_bf16"] = rb
         outs[name] = o
     torch.cuda.synchronize()
     for kind in ("bf16", "gelu", "res_bf16"):
-        assert not torch.isnan(outs["pp"][kind]).any(), kind
-        assert torch.equal(outs["pp"][kind], outs["t128"][kind]), kind
+        for name in ("pp", "ppf"):
+            assert not torch.isnan(outs[name][kind]).any(), (name, kind)
+            assert torch.equal(outs[name][kind], outs["t128"][kind]), (name, kind)
     rows = torch.tensor([0, 255, 256 * 8 - 1, 256 * 8, 256 * 256 + 3, M - 1])
     ref = bf((bf(A[rows]).double() @ bf(W).double().T + bf(bias).double()).float()).float()
     got = outs["pp"]["bf16"][rows.to(DEV)].float().cpu()
@@ -375,25 +401,31 @@ def test_gemm_sk_tail_forward(M, N, K):
     bias = torch.randn(N, generator=g)
     Ad, Wd, bd = bf(A).to(DEV), bf(W).to(DEV), bf(bias).to(DEV)
     res0 = bf(torch.randn(M, N, generator=g)).to(DEV)
-    outs = {}
+    # on 256 CUs: (m-tile rows of the whole rounds, K chunks of the tail)
+    want = {"t128": ("t128", 0, 0), "sk": ("rounds_sk_tail",) + {28608: (102, 5), 11000: (42, 8), 512: (0, 16)}[M]}
+    outs, routes = {}, []
     for name, f in (("t128", ops.GEMM_TILE128), ("sk", 0)):
         o = {}
+
+        def gemm(*a, **kw):                              # the route first, then the product
+            r = route_of(*a, **kw)
+            assert (r.route, r.m_dp, r.S) == want[name], (name, r)
+            routes.append(r)
+            ops.gemm(*a, **kw)
         C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
-        ops.gemm(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, flags=ops.GEMM_ROUND | f)
         o["bf16"] = C
         Cg = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
         aux = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
-        ops.gemm(Ad, Wd, Cg, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, aux=aux, ldaux=N,
-                 flags=ops.GEMM_ROUND | ops.GEMM_GELU | ops.GEMM_AUX_OUT | f)
+        gemm(Ad, Wd, Cg, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, aux=aux, ldaux=N,
+             flags=ops.GEMM_ROUND | ops.GEMM_GELU | ops.GEMM_AUX_OUT | f)
         o["gelu"], o["aux"] = Cg, aux
         rb = res0.clone()
-        ops.gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
+        gemm(Ad, Wd, rb, M, N, K, lda=K, ldb=K, ldc=N, bias=bd, res=rb, ldr=N, flags=ops.GEMM_ROUND | f)
         o["res_bf16"] = rb
         outs[name] = o
     torch.cuda.synchronize()
-    cus = torch.cuda.get_device_properties(0).multi_processor_count & ~7
-    tn, tm = (N + 255) // 256, (M + 255) // 256
-    m_dp = (tn * tm // cus) * cus // tn * 256                # rows of the whole rounds (0 below one round)
+    m_dp = routes[-1].m_dp * 256                             # rows of the whole rounds (0 below one round)
     assert 0 <= m_dp < M
     same_pre = outs["sk"]["aux"][m_dp:] == outs["t128"]["aux"][m_dp:]
     for kind in ("bf16", "gelu", "aux", "res_bf16"):
@@ -422,8 +454,9 @@ def test_gemm_sk_tail_forward(M, N, K):
 
 def test_transpose_and_long_k_head_grad():
     """The LM-head input gradient at the vocabulary K: E transposed to K-major (tw_transpose_bf16, exact,
-    ragged edges) and the K = 51 904 product on the persistent kernel == the MN-major product on the 128x128
-    kernel bit for bit (same K order)."""
+    ragged edges) and the K = 51 904 K-major product == the MN-major product on the 128x128 kernel bit for bit (same
+    K order).  The K-major product's default route on 256 CUs (275 256-tiles) is whole rounds on the persistent
+    kernel, 51 m-tile rows, plus a 128x128 tail; the forced persistent kernel is compared as well."""
     from tw import ops
     g = torch.Generator(device=DEV).manual_seed(3)
     for rows, cols in ((100, 70), (51904, 1280), (333, 1000)):
@@ -437,10 +470,19 @@ def test_transpose_and_long_k_head_grad():
     ET = ops.transpose_bf16(E, torch.empty(d, V, dtype=torch.bfloat16, device=DEV))
     a = torch.empty(M, d, dtype=torch.bfloat16, device=DEV)
     b = torch.empty(M, d, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(dl, ET, a, M, d, V, lda=V, ldb=V, ldc=d, flags=ops.GEMM_ROUND)                       # persistent
-    ops.gemm(dl, E, b, M, d, V, lda=V, ldb=d, ldc=d, b_trans=True, flags=ops.GEMM_ROUND | ops.GEMM_TILE128)
+    c = torch.empty(M, d, dtype=torch.bfloat16, device=DEV)
+    r = route_of(dl, ET, a, M, d, V, lda=V, ldb=V, ldc=d, flags=ops.GEMM_ROUND)
+    assert (r.route, r.m_dp) == ("rounds_dp_tail", 51), r
+    ops.gemm(dl, ET, a, M, d, V, lda=V, ldb=V, ldc=d, flags=ops.GEMM_ROUND)       # whole rounds persistent + 128x128 tail
+    pp = ops.GEMM_ROUND | ops.GEMM_TILE256PP
+    assert route_of(dl, ET, c, M, d, V, lda=V, ldb=V, ldc=d, flags=pp).route == "persistent"
+    ops.gemm(dl, ET, c, M, d, V, lda=V, ldb=V, ldc=d, flags=pp)                                   # persistent
+    t128 = ops.GEMM_ROUND | ops.GEMM_TILE128
+    assert route_of(dl, E, b, M, d, V, lda=V, ldb=d, ldc=d, b_trans=True, flags=t128).route == "t128"
+    ops.gemm(dl, E, b, M, d, V, lda=V, ldb=d, ldc=d, b_trans=True, flags=t128)
     torch.cuda.synchronize()
     assert torch.equal(a, b)
+    assert torch.equal(c, b)
 
 
 @pytest.mark.parametrize("N,K,M", [(1280, 1280, 28608), (2560, 1280, 8192), (264, 136, 4096), (1280, 1280, 1000)])
@@ -455,11 +497,18 @@ def test_gemm_splitk_weight_grad(N, K, M):
     dyd, xd = bf(dy).to(DEV), bf(x).to(DEV)
     base = torch.randn(N, K, generator=g)
     ref = bf((bf(dy).double().T @ bf(x).double()).float()).double() + base.double()
+    # the default call's (K chunks, tile) on 256 CUs; M = 1000 tokens is below two chunks of 512: unsplit
+    split = {28608: (8, 256), 8192: (4, 256), 4096: (8, 128), 1000: None}[M]
     outs = []
     for f in (0, ops.GEMM_NOSPLIT):
         dw = base.clone().to(DEV)
-        ops.gemm(dyd, xd, dw, N, K, M, lda=N, ldb=K, ldc=K, a_trans=True, b_trans=True,
-                 flags=ops.GEMM_ROUND | ops.GEMM_ACCUM | f)
+        kw = dict(lda=N, ldb=K, ldc=K, a_trans=True, b_trans=True, flags=ops.GEMM_ROUND | ops.GEMM_ACCUM | f)
+        r = route_of(dyd, xd, dw, N, K, M, **kw)
+        if f == 0 and split:
+            assert (r.route, r.S, r.split_tile) == ("splitk_dw",) + split, r
+        else:
+            assert (r.route, r.S) == ("t128", 0), r
+        ops.gemm(dyd, xd, dw, N, K, M, **kw)
         torch.cuda.synchronize()
         outs.append(dw.cpu())
     prod = torch.maximum((outs[0] - base).abs(), (outs[1] - base).abs())
@@ -477,9 +526,10 @@ def test_gemm_splitk_weight_grad(N, K, M):
                                    (128, 200, 64), (128, 1280, 5120), (65, 520, 1280), (512, 1280, 1280),
                                    (300, 3840, 1280)])
 def test_gemm_skinny_decode_path(M, N, K):
-    """M <= 512 K-major GEMMs (decode steps) take the weight-streaming kernel (above 64 rows as 64-row
-    blocks, the last one ragged unless M % 64 == 0); every epilogue kind against fp64 (tolerance: one bf16 ulp of
-    the largest value; fp32 out 1e-5 relative)."""
+    """Decode-step K-major GEMMs: M <= 128 rows take the weight-streaming kernel (above 64 rows as 64-row
+    blocks, the last one ragged unless M % 64 == 0; with the K range split over workgroups where the grid is small
+    and M > 32), the two wider batches the 128x128 tiles on the 4-stage ring; every epilogue kind against fp64
+    (tolerance: one bf16 ulp of the largest value; fp32 out 1e-5 relative)."""
     from tw import ops
     g = torch.Generator().manual_seed(M * 7 + N + K)
     A, W = torch.randn(M, K, generator=g), torch.randn(N, K, generator=g) * 0.05
@@ -488,6 +538,12 @@ def test_gemm_skinny_decode_path(M, N, K):
     acc = bf(A).double() @ bf(W).double().T
     y = bf((acc + bf(bias).double()).float()).float()
     C = torch.empty(M, N, device=DEV)
+    want = {(1, 16, 8): ("skinny", 1), (5, 1000, 1280): ("skinny", 1), (64, 1280, 5120): ("skinny_splitk", 7),
+            (100, 3840, 1280): ("skinny_splitk", 2), (128, 200, 64): ("skinny", 1), (128, 1280, 5120): ("skinny_splitk", 4),
+            (65, 520, 1280): ("skinny_splitk", 8), (512, 1280, 1280): ("t128_ring4", 0),
+            (300, 3840, 1280): ("t128_ring4", 0)}[(M, N, K)]           # on 256 CUs
+    r = route_of(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N)
+    assert (r.route, r.S) == want, r
     ops.gemm(Ad, Wd, C, M, N, K, lda=K, ldb=K, ldc=N)
     assert rel_err(C, acc) < 1e-5
     Cg, aux = torch.empty(M, N, dtype=torch.bfloat16, device=DEV), torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
