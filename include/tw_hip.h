@@ -329,6 +329,24 @@ int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dtype, int B,
                         int* last_ts, const uint32_t* ctl, float* sum_logp, tw_stream_t stream);
 int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, int V, int token, float* out,
                      tw_stream_t stream);
+/* tw_repeat_process: HF RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor (logits_process.py;
+ * generate(repetition_penalty=, no_repeat_ngram_size=)), the two processors GenerationMixin._get_logits_processor
+ * runs before Whisper's own -- a pre-pass in front of the selection kernels above, which then take `out` as an fp32
+ * row.  For each row b, out[b*ld_out + 0..V) = the first V logits of the row as fp32 (bf16, fp16 or fp32 in; the
+ * output is always fp32 and never in place: HF upcasts 16-bit logits before any processor, and a penalised value
+ * rounded back to 16 bits would move ties), processed for the history ids[b*ld_ids + 0..L), L = col + (t_dev ?
+ * *t_dev : 0) -- the column the selection kernel is about to write; the whole decoder row so far counts, pad and
+ * prompt columns included, as in HF:
+ *   penalty != 1: every distinct token u of the history gets s[u] < 0 ? s[u] * penalty : s[u] / penalty, one
+ *     correctly rounded fp32 operation on the unpenalised score (-0.0 and NaN take the quotient);
+ *   ngram > 0: for every i in [0, L - ngram] with ids[i .. i+ngram-1) == ids[L-ngram+1 .. L), s[ids[i+ngram-1]] =
+ *     -inf, after the penalty (ngram 1 bans every token of the history; L < ngram bans nothing).
+ * penalty 1 and ngram 0 copy the row.  History ids outside [0, V) are ignored.  Input columns [V, ld) are never
+ * used (they may hold NaN), output columns [V, ld_out) are not written.  Returns 1 for penalty <= 0 (or NaN),
+ * ngram < 0, col < 0, B <= 0, V <= 0, ld < V or ld_out < V, 2 for another dtype; nothing is written then. */
+int tw_repeat_process(const void* logits, int64_t ld, int logits_dtype, int B, int V, const int64_t* ids,
+                      int64_t ld_ids, int col, const int* t_dev, float penalty, int ngram, float* out, int64_t ld_out,
+                      tw_stream_t stream);
 int tw_embed_step(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
                   int out_dtype, int B, int D, const int* t_dev, tw_stream_t stream);
 /* tw_embed_step_off: out[b] = tok[ids[b]] + pos[max(*t_dev - pos_off[b], 0)] -- pos_off a device array of B int32,

@@ -2,7 +2,8 @@
 synthetic 30 s features; eos is suppressed so every clip runs exactly --new-tokens steps
 (deterministic work, as §8d prescribes: max_new_tokens 224).
 
-    python tools/bench_decode.py [--batch 64] [--new-tokens 224] [--clips 128] [--eager]
+    python tools/bench_decode.py [--batch 64] [--new-tokens 224] [--clips 128] [--eager] [--dtype float16]
+                                 [--repetition_penalty 1.3] [--no_repeat_ngram_size 3]
 """
 import argparse
 import os
@@ -20,6 +21,9 @@ def main():
     ap.add_argument("--clips", type=int, default=128)
     ap.add_argument("--config", default="large-v2")
     ap.add_argument("--eager", action="store_true")
+    ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16"])
+    ap.add_argument("--repetition_penalty", type=float, default=1.0)
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0)
     ap.add_argument("--longform-seconds", type=float, default=0.0,
                     help="config c5: one input of this many seconds, return_timestamps, --new-tokens per window")
     a = ap.parse_args()
@@ -28,7 +32,9 @@ def main():
     from tw.config import GenerationConfig, WhisperConfig
     from tw.modeling import WhisperForConditionalGeneration, random_init_
     cfg = WhisperConfig(**CONFIGS[a.config])
-    m = WhisperForConditionalGeneration(cfg, dtype=torch.bfloat16)
+    m = WhisperForConditionalGeneration(cfg, dtype=getattr(torch, a.dtype))
+    if a.dtype == "float16":
+        m.set_compute("fp16")
     random_init_(m, seed=0)
     m.generation_config = GenerationConfig(suppress_tokens=[50257], begin_suppress_tokens=[220, 50257],
                                            lang_to_id={"<|zh|>": 50260})
@@ -49,18 +55,20 @@ def main():
               f"{out.shape[1]} output tokens: {dt:.2f} s wall ({a.longform_seconds / dt:.1f}x real time, "
               f"{dt / max(steps, 1) * 1e3:.2f} ms/step at batch 1)", flush=True)
         return
+    rep = dict(repetition_penalty=a.repetition_penalty, no_repeat_ngram_size=a.no_repeat_ngram_size)
     feats = torch.randn(a.batch, 80, 3000, device="cuda") * 0.3
-    m.generate(feats[:2], language="zh", task="transcribe", max_new_tokens=4, use_graph=not a.eager)   # warm-up
+    m.generate(feats[:2], language="zh", task="transcribe", max_new_tokens=4, use_graph=not a.eager, **rep)   # warm-up
     torch.cuda.synchronize()
     n_sub = max(1, a.clips // a.batch)
     t0 = time.perf_counter()
     for _ in range(n_sub):
         out = m.generate(feats, language="zh", task="transcribe", max_new_tokens=a.new_tokens,
-                         use_graph=not a.eager)
+                         use_graph=not a.eager, **rep)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     clips = n_sub * a.batch
-    print(f"c4 greedy {a.config}: {clips} clips x {out.shape[1]} tokens, batch {a.batch}: {dt:.2f} s "
+    print(f"c4 greedy {a.config} {a.dtype} penalty {a.repetition_penalty} ngram {a.no_repeat_ngram_size}: "
+          f"{clips} clips x {out.shape[1]} tokens, batch {a.batch}: {dt:.2f} s "
           f"-> {clips / dt:.2f} clips/s, {dt / n_sub / a.new_tokens * 1e3:.2f} ms/step "
           f"({'eager' if a.eager else 'graph'})", flush=True)
 

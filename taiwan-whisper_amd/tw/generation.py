@@ -321,8 +321,14 @@ class _Select:
     """Per-step token selection into ids[:, t+1] (t read on the device): HF SuppressTokens,
     SuppressTokensAtBegin and, with timestamps, WhisperTimeStampLogitsProcessor + argmax."""
 
-    def __init__(self, gc, B, V, T_max, P, dev, timestamps, track=False):
+    def __init__(self, gc, B, V, T_max, P, dev, timestamps, track=False, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0, Vp=None):
         self.V, self.P, self.ts, self.track = V, P, timestamps, track
+        # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor: launch-time scalars of the pre-pass
+        # (baked into a captured step) and its fp32 output rows [B][Vp]; neither active: no scratch, today's calls
+        self.penalty, self.ngram = float(repetition_penalty), int(no_repeat_ngram_size)
+        self.repeat = self.penalty != 1.0 or self.ngram > 0
+        self.scratch = torch.empty(B, Vp, dtype=torch.float32, device=dev) if self.repeat else None
         self.eos = int(gc.eos_token_id)
         self.sup = F.token_bitmask(gc.suppress_tokens or [], V, dev)
         self.beg = F.token_bitmask(gc.begin_suppress_tokens or [], V, dev)
@@ -359,8 +365,14 @@ class _Select:
     def launch(self, logits, t_dev, next_ids, col=1, sum_logp=None, B=1):
         """The selection kernel this selector's mode takes (plain, timestamps, or the tracking forms with their
         per-row control word) on `logits` ([B][Vp] rows) into ids[:, *t_dev + col] and next_ids.  sum_logp: where the
-        tracking forms accumulate (default: the selector's running sum)."""
+        tracking forms accumulate (default: the selector's running sum).  With a repetition penalty or a no-repeat
+        n-gram size, tw_repeat_process first writes the rows, processed for the history ids[:, :*t_dev + col], to the
+        selector's fp32 scratch, and the selection kernel reads that instead (HF runs the two processors first)."""
         Vp = logits.stride(0)
+        if self.repeat:
+            assert B <= self.scratch.shape[0] and Vp == self.scratch.shape[1]
+            logits = F.repeat_process(logits, Vp, B, self.V, self.ids, col, self.scratch[:B], self.penalty,
+                                      self.ngram, t_dev=t_dev)
         if self.track:
             slp = self.sum_logp if sum_logp is None else sum_logp
             if self.ts:
@@ -421,10 +433,12 @@ class _Decoder(_PromptedDecode):
     """One greedy decode of B windows with a fixed prompt; reusable across windows (long-form):
     the captured step graph stays valid because every buffer it touches is reused in place."""
 
-    def __init__(self, model, gc, B, Tk, P, max_length, timestamps, use_graph, track=False):
+    def __init__(self, model, gc, B, Tk, P, max_length, timestamps, use_graph, track=False, repetition_penalty=1.0,
+                 no_repeat_ngram_size=0):
         self.m, self.P, self.T_max, self.use_graph = model, P, max_length, use_graph
         self.sess = None
-        self.sel = _Select(gc, B, model.config.vocab_size, max_length, P, model.device, timestamps, track)
+        self.sel = _Select(gc, B, model.config.vocab_size, max_length, P, model.device, timestamps, track,
+                           repetition_penalty, no_repeat_ngram_size, Vp=model.Vp)
         self.B, self.Tk = B, Tk
         self.ns_logp = torch.zeros(B, dtype=torch.float32, device=model.device) if track else None
 
@@ -805,7 +819,32 @@ def retrieve_segment(seq, seek_num_frames, ts_begin=50364, input_stride=2):
 # keywords generate implements beyond its named parameters (the fallback settings of HF's long-form generate, the
 # engine's own switches and the tests' private hooks); anything else raises TypeError instead of being dropped
 GENERATE_KEYWORDS = frozenset({"temperature", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
-                               "condition_on_prev_tokens", "do_sample", "seed", "fallback_batch", "_trace", "_keep"})
+                               "condition_on_prev_tokens", "do_sample", "seed", "fallback_batch", "_trace", "_keep",
+                               "repetition_penalty", "no_repeat_ngram_size"})
+
+
+def repeat_options(gc, kw):
+    """generate's repetition_penalty / no_repeat_ngram_size -> (penalty, n): the call's value, else the generation
+    config's when it names one (as HF merges them), else off (1.0, 0).  HF's checks: the penalty a strictly positive
+    float (RepetitionPenaltyLogitsProcessor; 1 adds no processor, so an int 1 passes), the size a non-negative int."""
+    def pick(name):
+        v = kw.get(name)
+        return v if v is not None else (gc.get(name) if gc is not None and hasattr(gc, "get") else None)
+    p, n = pick("repetition_penalty"), pick("no_repeat_ngram_size")
+    if p is None or (not isinstance(p, bool) and isinstance(p, (int, float)) and p == 1):
+        p = 1.0
+    elif not isinstance(p, float) or not p > 0:
+        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p!r}")
+    if n is None:
+        n = 0
+    elif isinstance(n, bool) or not isinstance(n, int) or n < 0:
+        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {n!r}")
+    return float(p), int(n)
+
+
+def _repeat_names(penalty, ngram):
+    return " and ".join(nm for nm, on in (("repetition_penalty", penalty != 1.0), ("no_repeat_ngram_size", ngram > 0))
+                        if on)
 
 
 @torch.no_grad()
@@ -824,7 +863,13 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     WhisperForCausalLM decoding over this model's encoder output (the distilled student with the shared frozen
     encoder); it drafts num_assistant_tokens tokens a round (default DEFAULT_ASSISTANT_TOKENS, at most
     MAX_ASSISTANT_TOKENS; HF's default and schedule differ) and this model verifies them in one pass (_SpecDecoder).
-    The ids are those of the same call without an assistant.  Any keyword that is not implemented raises TypeError."""
+    The ids are those of the same call without an assistant.
+    repetition_penalty / no_repeat_ngram_size (HF generate's, faster-whisper transcribe's): HF's
+    RepetitionPenaltyLogitsProcessor and NoRepeatNGramLogitsProcessor on the raw fp32 scores of every generated step,
+    before the suppress / timestamp rules, the log-prob of the fallback gate and sampling; the history is the whole
+    decoder row (left padding, <|startofprev|> text and task prompt included).  Defaults come from generation_config
+    when it names them.  Greedy and long-form (fallback, condition_on_prev_tokens) decoding take them; beam search and
+    assisted decoding raise NotImplementedError.  Any keyword that is not implemented raises TypeError."""
     from .config import GenerationConfig
     unknown = sorted(set(kw) - GENERATE_KEYWORDS)
     if unknown:
@@ -860,6 +905,16 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     if gc.eos_token_id is None:
         gc.eos_token_id = model.config.eos_token_id
     cfg = model.config
+    penalty, ngram = repeat_options(gc, kw)
+    if penalty != 1.0 or ngram > 0:
+        # HF's beam search applies the two processors to log-probabilities, and the verify pass of assisted decoding
+        # would need a history per query row: neither is built
+        if nb > 1:
+            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with beam search (num_beams > 1) "
+                                      "is not implemented")
+        if assist is not None:
+            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with assisted decoding "
+                                      "(assistant_model) is not implemented")
     use_graph = True if use_graph is None else use_graph
     window = 2 * cfg.max_source_positions                     # 3000 feature frames = 30 s
     # HF (generation_whisper.py:785-898) runs the seek loop for every input when timestamps are predicted, a
@@ -869,7 +924,8 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     if encoder_outputs is None and input_features is not None and (input_features.shape[-1] > window or seek_loop):
         return _longform(model, gc, input_features, attention_mask, language, task, max_length, max_new_tokens,
                          use_graph, window, kw.get("_trace"), fallback_batch=bool(kw.get("fallback_batch", True)),
-                         num_beams=nb, prompt_ids=prompt_ids, assist=assist, **fb)
+                         num_beams=nb, prompt_ids=prompt_ids, assist=assist, repetition_penalty=penalty,
+                         no_repeat_ngram_size=ngram, **fb)
     if kw.get("do_sample") or fb["temperature"] not in (0, 0.0) or fb["logprob_threshold"] is not None \
             or fb["compression_ratio_threshold"] is not None or fb["no_speech_threshold"] is not None:
         # the reference applies fallback / thresholds to long-form inputs only (run_eval.py:659-685)
@@ -910,7 +966,8 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if not bool((prompt == prompt[:1]).all()):
             raise NotImplementedError("tw generate: beam search takes one prompt for every clip")
         return _BeamDecoder(model, gc, B, nb, Tk, P, max_length).run(enc16, prompt[0])
-    dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph)
+    dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph,
+                   **(dict(repetition_penalty=penalty, no_repeat_ngram_size=ngram) if penalty != 1.0 or ngram else {}))
     if kw.get("_keep") is not None:          # tests: the decoder (and its device caches) outlive the call
         kw["_keep"].append(dec)
     return dec.run(enc16, prompt.to(model.device))
@@ -1201,7 +1258,7 @@ def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace,
 def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
               trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
               no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
-              prompt_ids=None, assist=None):
+              prompt_ids=None, assist=None, repetition_penalty=1.0, no_repeat_ngram_size=0):
     """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from
     `seek`; each window decoded with timestamp rules at the first temperature of `temperature` and
     re-decoded at the next one while HF's fallback test fails (compression ratio of the token bytes,
@@ -1239,9 +1296,12 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
         sup = list(gc.suppress_tokens or [])
         prev_sot = sup[-2] if len(sup) >= 2 else None
     decoders = {}
+    # off: the decoders are built by today's call
+    repeat_kw = (dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
+                 if repetition_penalty != 1.0 or no_repeat_ngram_size > 0 else {})
 
     def decoder(P, ml, nb=1, spec=False):
-        key = (P, ml, nb, spec)
+        key = (P, ml, nb, spec, repetition_penalty, no_repeat_ngram_size)    # both are baked into a captured step
         if key in decoders:
             decoders[key] = decoders.pop(key)            # most recently used last
         else:
@@ -1253,7 +1313,8 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
                 decoders[key] = _SpecDecoder(model, assist[0], gc, cfg.max_source_positions, P, ml, True, use_graph,
                                              track, k=assist[1])
             else:
-                decoders[key] = _Decoder(model, gc, nb, cfg.max_source_positions, P, ml, True, use_graph, track)
+                decoders[key] = _Decoder(model, gc, nb, cfg.max_source_positions, P, ml, True, use_graph, track,
+                                         **repeat_kw)
         return decoders[key]
 
     def trim(raw):

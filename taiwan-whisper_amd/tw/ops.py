@@ -697,6 +697,21 @@ def select_sample_ts(logits, ld, B, V, suppress_bits, begin_bits, eos, done, ids
          ctl.data_ptr(), sum_logp.data_ptr(), _stream())
 
 
+def repeat_process(logits, ld, B, V, ids, col, out, penalty=1.0, ngram=0, t_dev=None):
+    """HF RepetitionPenaltyLogitsProcessor + NoRepeatNGramLogitsProcessor on the step's logits, for the history
+    ids[:, :col + *t_dev] -> out (float32 rows of stride out.stride(0)), which the selection wrappers above take as
+    their logits (tw_repeat_process)."""
+    assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.stride(1) == 1 and out.device == logits.device
+    assert t_dev is None or t_dev.dtype == torch.int32
+    _need(logits, (B - 1) * ld + V, "repeat logits")
+    _need(out, (B - 1) * out.stride(0) + V, "repeat out")
+    _need(ids, (B - 1) * ids.stride(0) + (ids.shape[1] if t_dev is not None else col), "repeat ids")
+    call("tw_repeat_process", logits.data_ptr(), ld, _dt(logits), B, V, ids.data_ptr(), ids.stride(0), int(col),
+         _ptr(t_dev), float(penalty), int(ngram), out.data_ptr(), out.stride(0), _stream())
+    return out
+
+
 def token_logprob(logits, ld, B, V, token, out):
     """out[b] = log_softmax(logits[b, :V])[token] (float32)."""
     assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and out.dtype == torch.float32

@@ -60,6 +60,11 @@ def parse_args(argv=None):
     ap.add_argument("--num_workers", type=int, default=8, help="host audio-decoding threads")
     ap.add_argument("--max_new_tokens", type=int, default=None)
     ap.add_argument("--byte_level_text_tokenizer", type=_bool, default=False)
+    # faster-whisper transcribe()'s names and defaults
+    ap.add_argument("--repetition_penalty", type=float, default=1.0,
+                    help="penalty on tokens already in the decoder row (> 1 penalises; 1.0: off)")
+    ap.add_argument("--no_repeat_ngram_size", type=int, default=0,
+                    help="no n-gram of this size may occur twice in the decoder row (0: off)")
     return ap.parse_args(argv)
 
 
@@ -97,7 +102,8 @@ class ChunkTranscriber:
     """Batched greedy transcription of <= 30 s chunks: GPU log-mel of the zero-padded chunk, encoder,
     KV-cache greedy decode.  Returns the generated ids per chunk (eos and padding removed)."""
 
-    def __init__(self, model, language: str = "zh", max_new_tokens: Optional[int] = None, device=None):
+    def __init__(self, model, language: str = "zh", max_new_tokens: Optional[int] = None, device=None,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
         from .feature_extraction import WhisperFeatureExtractor
         from .data import SpecialTokens
         self.m = model
@@ -105,13 +111,16 @@ class ChunkTranscriber:
         self.fe = WhisperFeatureExtractor(feature_size=model.config.num_mel_bins, device=device or model.device)
         self.eot = SpecialTokens.for_vocab(model.config.vocab_size).eot
         self.language, self.max_new_tokens = language, max_new_tokens
+        self.repetition_penalty, self.no_repeat_ngram_size = float(repetition_penalty), int(no_repeat_ngram_size)
 
     def __call__(self, chunks: Sequence[np.ndarray]) -> List[List[int]]:
         if not chunks:
             return []
         wav = self.fe.pad_waveforms(list(chunks))
         mel, _ = self.fe.extract(wav, want_conv_input=False)
-        ids = self.m.generate(mel, language=self.language, task="transcribe", max_new_tokens=self.max_new_tokens)
+        ids = self.m.generate(mel, language=self.language, task="transcribe", max_new_tokens=self.max_new_tokens,
+                              repetition_penalty=self.repetition_penalty,
+                              no_repeat_ngram_size=self.no_repeat_ngram_size)
         out = []
         for row in ids.tolist():
             k = row.index(self.eot) if self.eot in row else len(row)
@@ -255,7 +264,8 @@ def main(argv=None):
         args.model_size_or_path, torch_dtype=dtype, device=torch.device("cuda", local), compute=compute)
     print(f"Using device: cuda:{local} ({compute})", flush=True)
     decode = load_text_decoder(args)
-    tr = ChunkTranscriber(model, args.language, args.max_new_tokens)
+    tr = ChunkTranscriber(model, args.language, args.max_new_tokens, repetition_penalty=args.repetition_penalty,
+                          no_repeat_ngram_size=args.no_repeat_ngram_size)
     paths = load_dataset(args.dataset_path)[rank::world]
     os.makedirs(args.output_dir, exist_ok=True)
     def write(p, r):
