@@ -25,7 +25,9 @@ replayed per token; the host reads the finished flags every 8 steps to stop earl
 """
 from __future__ import annotations
 
+import dataclasses
 import time
+import types
 
 import torch
 
@@ -966,8 +968,8 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if not bool((prompt == prompt[:1]).all()):
             raise NotImplementedError("tw generate: beam search takes one prompt for every clip")
         return _BeamDecoder(model, gc, B, nb, Tk, P, max_length).run(enc16, prompt[0])
-    dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph,
-                   **(dict(repetition_penalty=penalty, no_repeat_ngram_size=ngram) if penalty != 1.0 or ngram else {}))
+    dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph, repetition_penalty=penalty,
+                   no_repeat_ngram_size=ngram)
     if kw.get("_keep") is not None:          # tests: the decoder (and its device caches) outlive the call
         kw["_keep"].append(dec)
     return dec.run(enc16, prompt.to(model.device))
@@ -1096,363 +1098,282 @@ def conditioned_prompts(init, segments, cond_on, conditioned, prev_sot, cut_off,
     return out, max(len(p) for p in out)
 
 
-def _longform_batched(model, gc, feats, lens, init, temps, track, window, trace, max_length, max_new_tokens,
-                      compression_ratio_threshold, logprob_threshold, no_speech_threshold, fallback_batch, decoder, trim,
-                      seeds_of, ns_token, ts_begin, eos, pad, enc_rows=32, n_task=None, cond=False, prev_sot=None,
-                      cut_off=None, assist=None):
-    """HF's batched sequential long-form (generation_whisper.py:785-898 with generate_with_fallback :970-1117): every
-    recording of the call stays in ONE batch window after window -- each seek iteration cuts the current 30 s window
-    of every unfinished recording at its own seek (_get_input_segment, zero-padded), encodes them together, decodes
-    them together from the same prompt, and a recording whose seek reaches its length leaves the batch
-    (_maybe_reduce_batch).  Fallback as generate_with_fallback: the rows whose attempt fails HF's gate are decoded
-    again at the next temperature, together; a row is accepted at its first passing attempt (or keeps its last one),
-    and a skipped row advances by its window.  run_eval.py:667-681 calls generate on inner_batch_size recordings this
-    way; HF's own rows are not batch-invariant either (the encoder and the decoder see the batch), so parity is with
-    HF's batched call (tests/test_batched_longform_gpu.py).
+def trim_pads(seq, pad, eos):
+    """seq without its trailing pads, as HF removes them (pad == eos keeps one eos)."""
+    seq = list(seq)
+    if seq and seq[-1] == pad:
+        k = len(seq)
+        while k > 1 and seq[k - 2] == pad:
+            k -= 1
+        seq = seq[:k] if pad == eos else seq[:k - 1]
+    return seq
 
-    Speculative fallback (fallback_batch, 16-bit paths whose decode rows are independent, batch_rows_independent):
-    while the failing rows are few, several temperature levels of them decode as one batch of at most 8 rows (the
-    decode step at <= 8 rows is one GEMV launch per Linear, latency-bound: extra rows are nearly free); each row still
-    takes its first passing attempt in temperature order, and a row's attempt decodes the same tokens whichever batch
-    it sits in (per-row temperature and seed, tw_select_sample_ts), so the result is the level-by-level one.
 
-    cond (condition_on_prev_tokens): the recordings stay in one batch too.  At each seek iteration every active row
-    builds its own prompt -- <|startofprev|> + the last cut_off tokens of its accepted segments + the task prompt,
-    conditioned only after a window accepted at temperature < 0.5 -- and the rows are left-padded with pad to the
-    longest prompt of the iteration (HF _prepare_decoder_input_ids / _pad_to_max_length, so HF's length cap, which
-    counts the padded length, is reproduced); the pad columns are masked per row on the device (_Decoder.run pads;
-    passed in every iteration of a conditioned call, all-zero counts included, so a decoder's captured step is not
-    dropped when equal and unequal prompt lengths alternate)
-    and every row embeds at its column index, as transformers 5.15 does (it passes the decoder attention mask but no
-    position ids for Whisper), so a padded row is HF's row, not the decode of its unpadded prompt.
-    As in HF, the conditioned form starts once recording 0 has a segment, and from then on a row without previous
-    text carries <|startofprev|> alone.  init: the unconditioned prompt (prompt_ids + task prompt); n_task: the
-    length of its task part (the <|startoftranscript|> position counts back from the end).
-    assist = (assistant, k) (one recording): the temperature-0 attempt of each window is assisted (_SpecDecoder: the
-    same tokens and gate values); sampled attempts use the plain decoder."""
-    model_cfg = model.config
-    dev = model.device
-    nmel = feats.shape[1]
-    B = feats.shape[0]
-    V = model_cfg.vocab_size
-    n_task = len(init) if n_task is None else n_task
-    spec = fallback_batch and batch_rows_independent(model)
-    seek = [0] * B
-    nwin = [0] * B
-    outs = [[] for _ in range(B)]
-    segments = [[] for _ in range(B)]          # accepted segments per recording (the previous text)
-    cond_on = [bool(cond)] * B
-    while True:
-        active = [b for b in range(B) if seek[b] < int(lens[b])]          # _maybe_reduce_batch
-        if not active:
-            break
-        nfr = {b: min(window, int(lens[b]) - seek[b]) for b in active}
-        prompts, P = conditioned_prompts(init, [segments[b] for b in active], [cond_on[b] for b in active],
-                                         any(cond_on) and len(segments[0]) > 0, prev_sot, cut_off, ts_begin)
-        prompts = dict(zip(active, prompts))
-        ml = total_length(model_cfg, gc, P, max_length, max_new_tokens)
-        if P >= ml:
-            raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
-        ns = (P - n_task, ns_token) if no_speech_threshold is not None else None
-        # encode the current windows together (chunks of enc_rows bound the encoder's activations)
-        enc, enc_as = {}, {}
-        for c0 in range(0, len(active), enc_rows):
-            rows = active[c0:c0 + enc_rows]
-            segb = torch.zeros(len(rows), nmel, window, dtype=torch.float32, device=dev)
-            for i, b in enumerate(rows):
-                segb[i, :, :nfr[b]] = feats[b, :, seek[b]:seek[b] + nfr[b]]
-            e = model.encode(model.conv_input(segb))
-            tk = e.shape[0] // len(rows)
-            for i, b in enumerate(rows):
-                enc[b] = e[i * tk:(i + 1) * tk]
-            if assist is not None:               # one recording: the assistant's rows for the same window
-                enc_as[rows[0]] = assistant_encoder(assist[0], model, enc[rows[0]], segb)
-            del segb
-        result = {}                       # b -> (accepted tokens, skip)
-        pending = list(active)
-        level = 0
-        seeds = {b: seeds_of(b, nwin[b]) for b in active}
-        while pending and level < len(temps):
-            per = max(1, 8 // len(pending)) if spec and level > 0 else 1
-            levels = list(range(level, min(len(temps), level + per)))
-            attempts = [(b, f) for f in levels for b in pending]
-            nb = _bucket(len(attempts))
-            pad_n = nb - len(attempts)
-            rows_att = attempts + [attempts[0]] * pad_n
-            one = len({b for b, _ in rows_att}) == 1
-            # the rows' encoder outputs: one window shared by every row (its K/V projected once), else gathered
-            e16 = enc[rows_att[0][0]] if one else torch.cat([enc[b] for b, _ in rows_att])
-            tl = [temps[f] or 0.0 for _, f in rows_att]
-            assisted = assist is not None and nb == 1 and not tl[0]
-            d_ = decoder(P, ml, nb, spec=assisted)
-            sl = [seeds[b][f] for b, f in rows_att]
-            pads = [P - len(prompts[b]) for b, _ in rows_att]
-            rows_p = [[pad] * n_ + prompts[b] for n_, (b, _) in zip(pads, rows_att)]
-            raws = d_.run(e16, torch.tensor(rows_p, dtype=torch.int64, device=dev),
-                          temperature=tl if nb > 1 else tl[0], seed=sl if nb > 1 else sl[0], no_speech=ns,
-                          **(dict(pads=pads) if cond else {}),
-                          **(dict(enc_a=enc_as[rows_att[0][0]]) if assisted else {})).tolist()
-            del e16
-            # a batch is cut at its LAST row's first eos: each row is cut at its own first eos, what its own decode
-            # returns
-            raws = [row_tokens(r, eos) for r in raws[:len(attempts)]]
-            decided = set()
-            for r, (b, f) in enumerate(attempts):
-                if b in decided:
-                    continue                                  # accepted at a lower temperature of this batch
-                raw = raws[r]
-                cand = trim(raw)
-                needs, skip = False, False
-                if track or compression_ratio_threshold is not None:
-                    tg = time.perf_counter()
-                    avg = float(d_.sel.sum_logp[r]) / max(len(cand), 1) if track else 0.0
-                    nsp = float(torch.exp(d_.ns_logp[r])) if ns is not None else 0.0
-                    needs, skip = need_fallback(cand, avg, nsp, V, compression_ratio_threshold, logprob_threshold,
-                                                no_speech_threshold)
+@dataclasses.dataclass
+class _LongForm:
+    """The constants of one long-form call, its decoder cache and the seek loop (`run`, once per group of recordings):
+    HF's batched sequential long-form (generation_whisper.py:785-898 with generate_with_fallback :970-1117).  The
+    recordings of a group stay in ONE batch window after window: each seek iteration cuts the current 30 s window of
+    every unfinished recording at its own seek (_get_input_segment, zero-padded), encodes and decodes them together,
+    and a recording whose seek reaches its length leaves the batch (_maybe_reduce_batch).  The rows whose attempt
+    fails HF's gate (compression ratio of the token bytes, average log-prob of the processed scores; no-speech
+    probability at <|startoftranscript|> -> the window is skipped) are decoded again at the next temperature,
+    together; a row is accepted at its first passing attempt (or keeps its last one).  HF's own rows are not
+    batch-invariant either, so parity is with HF's batched call (tests/test_batched_longform_gpu.py).
+    Speculative fallback (fallback_batch, where batch_rows_independent): while the failing rows are few, several
+    temperature levels of them decode as one batch of at most 8 rows (<= 8 rows is one GEMV launch per Linear,
+    latency-bound: extra rows are nearly free); a row's attempt decodes the same tokens whichever batch it sits in
+    (per-row temperature and seed, tw_select_sample_ts), so the result is the level-by-level one.
+    cond (condition_on_prev_tokens): every active row builds its own prompt -- <|startofprev|> + the last cut_off
+    tokens of its accepted segments + the task prompt, conditioned only after a window accepted at temperature < 0.5
+    -- and the rows are left-padded with pad to the longest prompt of the iteration (HF _prepare_decoder_input_ids /
+    _pad_to_max_length; HF's length cap counts the padded length); every row embeds at its column index, as
+    transformers 5.15 does, so a padded row is HF's row, not the decode of its unpadded prompt.  As in HF, the
+    conditioned form starts once the group's first recording has a segment, and from then on a row without previous
+    text carries <|startofprev|> alone (no <|startofprev|> id: the rows condition without it).
+    init: prompt_ids + task prompt, the unconditioned prompt; n_task: the length of its task part.  assist =
+    (assistant, k), one recording: the temperature-0 attempt of each window is assisted (_SpecDecoder)."""
+    model: object
+    gc: object
+    temps: tuple
+    track: bool
+    window: int
+    compression_ratio_threshold: float
+    logprob_threshold: float
+    no_speech_threshold: float
+    fallback_batch: bool
+    cond: bool
+    eos: int
+    pad: int
+    ts_begin: int
+    ns_token: int
+    prev_sot: int
+    cut_off: int
+    init: list
+    n_task: int
+    max_length: int
+    max_new_tokens: int
+    use_graph: bool
+    assist: tuple
+    repetition_penalty: float
+    no_repeat_ngram_size: int
+    num_beams: int
+    seed: int
+    trace: list
+    enc_rows: int = 32              # windows per encoder call (bounds the encoder's activations)
+    decoders: dict = dataclasses.field(default_factory=dict)
+
+    def decoder(self, P, ml, nb=1, spec=False):
+        # the two repeat options are baked into a captured step
+        key = (P, ml, nb, spec, self.repetition_penalty, self.no_repeat_ngram_size)
+        if key in self.decoders:
+            self.decoders[key] = self.decoders.pop(key)      # most recently used last
+        else:
+            # each decoder holds a captured step and the cross-attention K/V of its rows (246 MB per row at
+            # large-v2): keep the three most recently used
+            while len(self.decoders) >= 3:
+                self.decoders.pop(next(iter(self.decoders)))
+            m, Tk = self.model, self.model.config.max_source_positions
+            if spec:
+                self.decoders[key] = _SpecDecoder(m, self.assist[0], self.gc, Tk, P, ml, True, self.use_graph,
+                                                  self.track, k=self.assist[1])
+            else:
+                self.decoders[key] = _Decoder(m, self.gc, nb, Tk, P, ml, True, self.use_graph, self.track,
+                                              repetition_penalty=self.repetition_penalty,
+                                              no_repeat_ngram_size=self.no_repeat_ngram_size)
+        return self.decoders[key]
+
+    def seeds(self, b, nwin):
+        """One seed per temperature level for window nwin of recording b (its index in the call)."""
+        return [(self.seed * 1000003 + b * 7919 + nwin * 131 + fi) & ((1 << 63) - 1) for fi in range(len(self.temps))]
+
+    # One attempt of the fallback ladder on the window state w (enc, enc_a, prompts, P, ml, ns, seeds, padded) ->
+    # (raw tokens per attempt, gate(r, n) -> (avg_logprob over n tokens, no_speech_prob) of row r, read back only when
+    # the row is gated, decode batch, accepted drafts per round or None)
+    def decode_rows(self, w, attempts):
+        """`attempts` [(recording, level)] as one batch of _bucket rows, each with its own temperature and seed; rows
+        of one window share its encoder rows (K/V projected once).  A group of several conditioned recordings passes
+        the rows' pad counts in every iteration, all zeros included, so a decoder's captured step is not dropped when
+        equal and unequal prompt lengths alternate; a group of one has no padding and makes the plain calls."""
+        nb = _bucket(len(attempts))
+        rows = attempts + [attempts[0]] * (nb - len(attempts))
+        b0 = rows[0][0]
+        e16 = w.enc[b0] if len({b for b, _ in rows}) == 1 else torch.cat([w.enc[b] for b, _ in rows])
+        tl = [self.temps[f] or 0.0 for _, f in rows]
+        sl = [w.seeds[b][f] for b, f in rows]
+        assisted = self.assist is not None and nb == 1 and not tl[0]
+        dec = self.decoder(w.P, w.ml, nb, spec=assisted)
+        pads = [w.P - len(w.prompts[b]) for b, _ in rows]
+        prompt = torch.tensor([[self.pad] * n + w.prompts[b] for n, (b, _) in zip(pads, rows)], dtype=torch.int64,
+                              device=self.model.device)
+        kw = dict(temperature=tl if nb > 1 else tl[0], seed=sl if nb > 1 else sl[0], no_speech=w.ns)
+        if w.padded:
+            kw["pads"] = pads
+        if assisted:
+            kw["enc_a"] = w.enc_a[b0]
+        # a batch is cut at its LAST row's first eos: each row is cut at its own first eos, what its own decode returns
+        raws = [row_tokens(r, self.eos) for r in dec.run(e16, prompt, **kw).tolist()[:len(attempts)]]
+
+        def gate(r, n):
+            return (float(dec.sel.sum_logp[r]) / n if self.track else 0.0,
+                    float(torch.exp(dec.ns_logp[r])) if w.ns is not None else 0.0)
+        return raws, gate, nb, list(dec.accepted) if assisted else None
+
+    def decode_beam(self, w, b):
+        """HF generate_with_fallback at temperature 0 with num_beams > 1: a beam search over recording b's window
+        (_BeamDecoder with the timestamp rules; its gate values from the chosen hypothesis's per-step processed
+        scores).  One row, always gated."""
+        gc = self.gc
+        beam_ts = (self.ts_begin, int(gc.no_timestamps_token_id),
+                   gc.max_initial_timestamp_index if "max_initial_timestamp_index" in gc else None)
+        bd = _BeamDecoder(self.model, gc, 1, self.num_beams, self.model.config.max_source_positions, w.P, w.ml,
+                          timestamps=beam_ts)
+        raw = row_tokens(bd.run(w.enc[b], w.prompts[b], no_speech=w.ns)[0].tolist(), self.eos)
+
+        def gate(r, n):
+            return float(bd.sum_logp[0]) / n, float(bd.ns_prob[0]) if w.ns is not None else 0.0
+        return [raw], gate, 1, None
+
+    def run(self, feats, lens, recs):
+        """The seek loop over the recordings `recs` (their indices in the call) -> {recording: its tokens}."""
+        model, temps, window, eos, pad, trace = self.model, self.temps, self.window, self.eos, self.pad, self.trace
+        dev, nmel, V = model.device, feats.shape[1], model.config.vocab_size
+        spec = self.fallback_batch and batch_rows_independent(model)
+        # a beam search at temperature 0 later in the schedule decodes alone: the levels are taken one at a time
+        one_level = self.num_beams > 1 and any(not t for t in temps[1:])
+        assert self.num_beams == 1 or len(recs) == 1
+        seek = {b: 0 for b in recs}
+        nwin = {b: 0 for b in recs}
+        outs = {b: [] for b in recs}
+        segments = {b: [] for b in recs}         # accepted segments per recording (the previous text)
+        cond_on = {b: self.cond for b in recs}
+        while True:
+            active = [b for b in recs if seek[b] < int(lens[b])]          # _maybe_reduce_batch
+            if not active:
+                break
+            nfr = {b: min(window, int(lens[b]) - seek[b]) for b in active}
+            prompts, P = conditioned_prompts(self.init, [segments[b] for b in active], [cond_on[b] for b in active],
+                                             any(cond_on.values()) and len(segments[recs[0]]) > 0, self.prev_sot,
+                                             self.cut_off, self.ts_begin)
+            ml = total_length(model.config, self.gc, P, self.max_length, self.max_new_tokens)
+            if P >= ml:
+                raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
+            w = types.SimpleNamespace(enc={}, enc_a={}, prompts=dict(zip(active, prompts)), P=P, ml=ml,
+                                      ns=(P - self.n_task, self.ns_token) if self.no_speech_threshold is not None
+                                      else None, seeds={b: self.seeds(b, nwin[b]) for b in active},
+                                      padded=self.cond and len(recs) > 1)
+            # encode the current windows together (chunks of enc_rows)
+            for c0 in range(0, len(active), self.enc_rows):
+                rows = active[c0:c0 + self.enc_rows]
+                segb = torch.zeros(len(rows), nmel, window, dtype=torch.float32, device=dev)
+                for i, b in enumerate(rows):
+                    segb[i, :, :nfr[b]] = feats[b, :, seek[b]:seek[b] + nfr[b]]
+                e = model.encode(model.conv_input(segb))
+                tk = e.shape[0] // len(rows)
+                for i, b in enumerate(rows):
+                    w.enc[b] = e[i * tk:(i + 1) * tk]
+                if self.assist is not None:          # one recording: the assistant's rows for the same window
+                    w.enc_a[rows[0]] = assistant_encoder(self.assist[0], model, w.enc[rows[0]], segb)
+                del segb
+            result = {}                       # b -> (last attempt's tokens, skip, its temperature)
+            pending = list(active)
+            level = 0
+            while pending and level < len(temps):
+                per = max(1, 8 // len(pending)) if spec and level > 0 and not one_level else 1
+                levels = list(range(level, min(len(temps), level + per)))
+                attempts = [(b, f) for f in levels for b in pending]
+                beam = self.num_beams > 1 and len(levels) == 1 and not temps[level]
+                raws, gate, batch, accepted = self.decode_beam(w, pending[0]) if beam else self.decode_rows(w, attempts)
+                decided = set()
+                for r, (b, f) in enumerate(attempts):
+                    if b in decided:
+                        continue                                  # accepted at a lower temperature of this batch
+                    raw = raws[r]
+                    needs, skip = False, False
+                    rec = dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(w.prompts[b]), raw=list(raw))
+                    if self.track or self.compression_ratio_threshold is not None or beam:
+                        tg = time.perf_counter()      # gate cost: log-prob / no-speech readback + compression ratio
+                        cand = trim_pads(raw, pad, eos)
+                        avg, nsp = gate(r, max(len(cand), 1))
+                        needs, skip = need_fallback(cand, avg, nsp, V, self.compression_ratio_threshold,
+                                                    self.logprob_threshold, self.no_speech_threshold)
+                        rec.update(avg_logprob=avg, no_speech_prob=nsp, needs_fallback=needs, skip=skip, batch=batch,
+                                   gate_ms=(time.perf_counter() - tg) * 1e3)
+                    else:
+                        rec["batch"] = batch
+                    if accepted is not None:
+                        rec["accepted"] = accepted
                     if trace is not None:
-                        trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(prompts[b]), raw=list(raw),
-                                          avg_logprob=avg, no_speech_prob=nsp, needs_fallback=needs, skip=skip,
-                                          batch=nb, gate_ms=(time.perf_counter() - tg) * 1e3))
-                elif trace is not None:
-                    trace.append(dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(prompts[b]), raw=list(raw),
-                                      batch=nb))
-                if trace is not None and assisted:
-                    trace[-1]["accepted"] = list(d_.accepted)
-                result[b] = (raw, skip, temps[f])
-                if not needs:
-                    decided.add(b)
-            pending = [b for b in pending if b not in decided]
-            level = levels[-1] + 1
-        del enc, enc_as
-        for b in active:
-            seq, skip, t_acc = result[b]
-            n = nfr[b]
-            nwin[b] += 1
-            cond_on[b] = bool(cond) and (t_acc is None or t_acc < 0.5)
-            if skip:
-                seek[b] += n
-                continue
-            if seek[b] + window < int(lens[b]) and seq and seq[-1] == eos:    # not the last window: cut its eos
-                seq = seq[:-1]
-            if seq and seq[-1] == pad:                                         # trailing pads (pad == eos keeps one)
-                k = len(seq)
-                while k > 1 and seq[k - 2] == pad:
-                    k -= 1
-                seq = seq[:k] if pad == eos else seq[:k - 1]
-            if not seq:
-                seek[b] += n
-                continue
-            segs, off = retrieve_segment(seq, n, ts_begin)
-            for sgm in segs:
-                outs[b].extend(sgm)
-                if cond:
-                    segments[b].append(list(sgm))
-            seek[b] += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
-    L = max((len(o) for o in outs), default=0)
-    res = torch.full((B, L), pad, dtype=torch.int64)
-    for b, o in enumerate(outs):
-        res[b, :len(o)] = torch.tensor(o, dtype=torch.int64)
-    return res.to(dev)
+                        trace.append(rec)
+                    result[b] = (raw, skip, temps[f])
+                    if not needs:
+                        decided.add(b)
+                pending = [b for b in pending if b not in decided]
+                level = levels[-1] + 1
+            del w
+            for b in active:
+                seq, skip, t_acc = result[b]
+                n = nfr[b]
+                nwin[b] += 1
+                cond_on[b] = self.cond and (t_acc is None or t_acc < 0.5)
+                if not skip:
+                    if seek[b] + window < int(lens[b]) and seq and seq[-1] == eos:    # not the last window: cut its eos
+                        seq = seq[:-1]
+                    seq = trim_pads(seq, pad, eos)
+                if skip or not seq:
+                    seek[b] += n
+                    continue
+                segs, off = retrieve_segment(seq, n, self.ts_begin)
+                for sgm in segs:
+                    outs[b].extend(sgm)
+                    if self.cond:
+                        segments[b].append(list(sgm))
+                seek[b] += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
+        return outs
 
 
 def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
               trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
               no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
               prompt_ids=None, assist=None, repetition_penalty=1.0, no_repeat_ngram_size=0):
-    """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from
-    `seek`; each window decoded with timestamp rules at the first temperature of `temperature` and
-    re-decoded at the next one while HF's fallback test fails (compression ratio of the token bytes,
-    average log-prob of the processed scores, no-speech probability at <|startoftranscript|> -> skip
-    the window); trailing eos/pad trimmed, segments split at consecutive timestamps, seek advanced
-    by the last timestamp (or the whole window on a single-timestamp ending).  With
-    condition_on_prev_tokens (and the accepted temperature < 0.5) the next window's prompt is
-    <|startofprev|> + the last max_target_positions // 2 - 1 tokens of the clip's segments (a
-    segment's closing timestamp of a double-timestamp ending dropped) + the task prompt; several
-    recordings still decode as one batch (_longform_batched, rows left-padded to the longest prompt).  Returns
-    the concatenated segment tokens, right-padded with pad.  Sampled windows draw from
-    softmax(x / T) with the engine's counter-based RNG (seeded by `seed`, the clip, the window and
-    the fallback index), not torch's RNG stream.  Once a window's first attempt fails, the remaining
-    temperatures are decoded together as one batch (fallback_batch; identical tokens and gates to decoding
-    them one by one, see the loop below).  num_beams > 1 (run_eval.py --num_beams with timestamps / long-form): as HF
-    generate_with_fallback, a temperature-0 attempt is a beam search over the window (_BeamDecoder with the timestamp
-    rules; its gates from the chosen hypothesis's per-step processed scores), a sampled attempt keeps one beam."""
+    """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from `seek`, decoded
+    with the timestamp rules and HF's temperature fallback; trailing eos/pad trimmed, segments split at consecutive
+    timestamps, seek advanced by the last timestamp (or the whole window on a single-timestamp ending).  Returns the
+    concatenated segment tokens, right-padded with pad.  Sampled attempts draw from softmax(x / T) with the engine's
+    counter-based RNG (seeded by `seed`, the recording, the window and the fallback index), not torch's RNG stream.
+    One seek loop (_LongForm.run) serves every form.  num_beams == 1: the recordings of the call are one group and
+    decode as one batch.  num_beams > 1 (run_eval.py --num_beams with timestamps / long-form): every recording is a
+    group of its own, in recording order, so each window is encoded alone (the encoder's output depends on the batch
+    it runs in); a temperature-0 attempt is a beam search over the window, a sampled attempt keeps one beam."""
     cfg = model.config
-    dev = model.device
-    feats = feats.to(dev, torch.float32)
-    B, nmel, T = feats.shape
+    feats = feats.to(model.device, torch.float32)
+    B, _, T = feats.shape
     lens = attention_mask.sum(-1).tolist() if attention_mask is not None else [T] * B
     task_init = build_prompt(gc, language, task, True)
-    init = list(prompt_ids or []) + task_init      # prompt_ids: in front of every window's task prompt (generate)
     temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (temperature,)
     track = (logprob_threshold is not None or no_speech_threshold is not None or any(t and t > 0 for t in temps)
              or len(temps) > 1)
     eos, pad = int(gc.eos_token_id), int(gc.pad_token_id if gc.pad_token_id is not None else gc.eos_token_id)
-    ts_begin = int(gc.no_timestamps_token_id) + 1
-    ns_token = int(gc.no_timestamps_token_id) - 1
-    V = cfg.vocab_size
-    cut_off = cfg.max_target_positions // 2 - 1
     prev_sot = gc.get("prev_sot_token_id") if hasattr(gc, "get") else None
     if prev_sot is None:
         sup = list(gc.suppress_tokens or [])
         prev_sot = sup[-2] if len(sup) >= 2 else None
-    decoders = {}
-    # off: the decoders are built by today's call
-    repeat_kw = (dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size)
-                 if repetition_penalty != 1.0 or no_repeat_ngram_size > 0 else {})
-
-    def decoder(P, ml, nb=1, spec=False):
-        key = (P, ml, nb, spec, repetition_penalty, no_repeat_ngram_size)    # both are baked into a captured step
-        if key in decoders:
-            decoders[key] = decoders.pop(key)            # most recently used last
-        else:
-            # each decoder holds a captured step and the cross-attention K/V of its rows (246 MB per row at
-            # large-v2): keep the three most recently used
-            while len(decoders) >= 3:
-                decoders.pop(next(iter(decoders)))
-            if spec:
-                decoders[key] = _SpecDecoder(model, assist[0], gc, cfg.max_source_positions, P, ml, True, use_graph,
-                                             track, k=assist[1])
-            else:
-                decoders[key] = _Decoder(model, gc, nb, cfg.max_source_positions, P, ml, True, use_graph, track,
-                                         **repeat_kw)
-        return decoders[key]
-
-    def trim(raw):
-        cand = list(raw)
-        if cand and cand[-1] == pad:                     # HF: padding removed except one eos
-            k = len(cand)
-            while k > 1 and cand[k - 2] == pad:
-                k -= 1
-            cand = cand[:k] if pad == eos else cand[:k - 1]
-        return cand
-
-    def seeds_of(b, nwin):
-        return [(seed * 1000003 + b * 7919 + nwin * 131 + fi) & ((1 << 63) - 1) for fi in range(len(temps))]
-
     nbeam = max(1, int(num_beams or 1))
-    beam_ts = (ts_begin, int(gc.no_timestamps_token_id), gc.max_initial_timestamp_index
-               if "max_initial_timestamp_index" in gc else None)
-    if nbeam == 1 and (not condition_on_prev_tokens or B > 1):
-        return _longform_batched(model, gc, feats, lens, init, temps, track, window, trace, max_length,
-                                 max_new_tokens, compression_ratio_threshold, logprob_threshold, no_speech_threshold,
-                                 fallback_batch, decoder, trim, seeds_of, ns_token, ts_begin, eos, pad,
-                                 n_task=len(task_init), cond=bool(condition_on_prev_tokens), prev_sot=prev_sot,
-                                 cut_off=cut_off, assist=assist)
-    # beam search, and conditioning on the previous windows' text for a single recording: one recording at a time
-    # (several conditioned recordings decode as one batch above, their prompts left-padded per row)
-    seg_in = torch.zeros(1, nmel, window, dtype=torch.float32, device=dev)
-    outs = []
-    for b in range(B):
-        Tb = int(lens[b])
-        seek, out, segments, nwin = 0, [], [], 0
-        cond = bool(condition_on_prev_tokens)
-        while seek < Tb:
-            n = min(window, Tb - seek)
-            seg_in.zero_()
-            seg_in[0, :, :n] = feats[b, :, seek:seek + n]
-            enc16 = model.encode(model.conv_input(seg_in))
-            prompt = list(init)
-            if cond and segments and prev_sot is not None:
-                prompt = [int(prev_sot)] + previous_text(segments, ts_begin)[-cut_off:] + init
-            P = len(prompt)
-            ml = total_length(cfg, gc, P, max_length, max_new_tokens)
-            if P >= ml:
-                raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
-            assisted = assist is not None and nbeam == 1 and not temps[0]      # the temperature-0 attempt
-            dec = decoder(P, ml, spec=assisted)
-            enc_a = assistant_encoder(assist[0], model, enc16, seg_in) if assisted else None
-            ptens = torch.tensor([prompt], dtype=torch.int64, device=dev)
-            ns = (P - len(task_init), ns_token) if no_speech_threshold is not None else None
-            skip, t_acc, seq = False, temps[0], []
-            # attempt fi draws with seed(fi); attempts 1.. run as ONE batch (one row per remaining temperature,
-            # speculatively) once attempt 0 fails its gate: a batch-1 decode step is launch-bound, so the
-            # batch costs about what one attempt does.  Rows are independent (per-row temperature / seed,
-            # tw_select_sample_ts), so each row decodes exactly the tokens its sequential attempt would, and the
-            # first passing row in temperature order is accepted, as HF generate_with_fallback accepts it.
-            seeds = seeds_of(b, nwin)
-            attempts = [(0, dec, enc16, ptens, [temps[0] or 0.0], [seeds[0]])]
-            rest = list(range(1, len(temps)))
-            # fallback_batch=False: one attempt at a time (A/B, tests); so does the fp32 compute path, whose rows are
-            # not shown independent of the batch (batch_rows_independent), and a beam search at temperature 0 later
-            # in the schedule
-            per = 8 if fallback_batch and batch_rows_independent(model) else 1
-            if nbeam > 1 and any(not temps[f] for f in rest):
-                per = 1
-            for fb in range(0, len(rest), per):
-                grp = rest[fb:fb + per]
-                attempts.append((grp[0], None, None, None, [temps[f] or 0.0 for f in grp], [seeds[f] for f in grp]))
-            for fi0, d_, e_, p_, tl, sl in attempts:
-                if nbeam > 1 and len(tl) == 1 and not tl[0]:   # temperature 0 with num_beams: the beam search
-                    bd = _BeamDecoder(model, gc, 1, nbeam, cfg.max_source_positions, P, ml, timestamps=beam_ts)
-                    raw = row_tokens(bd.run(enc16, prompt, no_speech=ns)[0].tolist(), eos)
-                    avg = float(bd.sum_logp[0]) / max(len(trim(raw)), 1)
-                    nsp = float(bd.ns_prob[0]) if ns is not None else 0.0
-                    raws, gates, nbatch = [raw], [(avg, nsp)], 1
-                else:
-                    if d_ is None:                           # a speculative batch of the remaining attempts
-                        nb = len(tl)
-                        d_ = decoder(P, ml, nb)
-                        e_ = enc16                           # shared by the rows (DecodeSession.set_encoder)
-                        p_ = ptens.repeat(nb, 1)
-                    raws = d_.run(e_, p_, temperature=tl if len(tl) > 1 else tl[0],
-                                  seed=sl if len(sl) > 1 else sl[0], no_speech=ns,
-                                  **(dict(enc_a=enc_a) if d_ is dec and assisted else {})).tolist()
-                    # a batch is cut at its LAST row's first eos, so a row that finished earlier carries extra eos
-                    # (=pad) columns; each row is cut at its own first eos, which is what its batch-1 decode returns
-                    raws = [row_tokens(r, eos) for r in raws]
-                    gates, nbatch = None, len(raws)
-                done_here = False
-                for r, raw in enumerate(raws):
-                    fi, temp = fi0 + r, temps[fi0 + r]
-                    cand = trim(raw)
-                    needs = False
-                    if track or compression_ratio_threshold is not None or (nbeam > 1 and gates is not None):
-                        tg = time.perf_counter()      # gate cost: log-prob / no-speech readback + compression ratio
-                        if gates is not None:
-                            avg, nsp = gates[r]
-                        else:
-                            avg = float(d_.sel.sum_logp[r]) / max(len(cand), 1) if track else 0.0
-                            nsp = float(torch.exp(d_.ns_logp[r])) if ns is not None else 0.0
-                        needs, skip = need_fallback(cand, avg, nsp, V, compression_ratio_threshold, logprob_threshold,
-                                                    no_speech_threshold)
-                        if trace is not None:
-                            trace.append(dict(b=b, seek=seek, n=n, T=temp, prompt=list(prompt), raw=list(raw),
-                                              avg_logprob=avg, no_speech_prob=nsp, needs_fallback=needs, skip=skip,
-                                              batch=nbatch, gate_ms=(time.perf_counter() - tg) * 1e3))
-                    elif trace is not None:
-                        trace.append(dict(b=b, seek=seek, n=n, T=temp, prompt=list(prompt), raw=list(raw),
-                                          batch=nbatch))
-                    if trace is not None and d_ is dec and assisted:
-                        trace[-1]["accepted"] = list(dec.accepted)
-                    seq, t_acc = raw, temp
-                    if not needs:
-                        done_here = True
-                        break
-                if done_here:
-                    break
-            nwin += 1
-            cond = bool(condition_on_prev_tokens) and (t_acc is None or t_acc < 0.5)
-            if skip:
-                seek += n
-                continue
-            if seek + window < Tb and seq and seq[-1] == eos:   # not the last window: cut a predicted eos
-                seq = seq[:-1]
-            if seq and seq[-1] == pad:                          # trailing pads (pad == eos keeps one)
-                k = len(seq)
-                while k > 1 and seq[k - 2] == pad:
-                    k -= 1
-                seq = seq[:k] if pad == eos else seq[:k - 1]
-            if not seq:
-                seek += n
-                continue
-            segs, off = retrieve_segment(seq, n, ts_begin)
-            for sgm in segs:
-                out.extend(sgm)
-                segments.append(list(sgm))
-            seek += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
-        outs.append(out)
-    L = max((len(o) for o in outs), default=0)
+    lf = _LongForm(model=model, gc=gc, temps=temps, track=track, window=window,
+                   compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
+                   no_speech_threshold=no_speech_threshold, fallback_batch=fallback_batch,
+                   cond=bool(condition_on_prev_tokens), eos=eos, pad=pad, ts_begin=int(gc.no_timestamps_token_id) + 1,
+                   ns_token=int(gc.no_timestamps_token_id) - 1, prev_sot=prev_sot,
+                   cut_off=cfg.max_target_positions // 2 - 1,
+                   init=list(prompt_ids or []) + task_init,    # prompt_ids: in front of every window's task prompt
+                   n_task=len(task_init), max_length=max_length, max_new_tokens=max_new_tokens, use_graph=use_graph,
+                   assist=assist, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                   num_beams=nbeam, seed=seed, trace=trace)
+    outs = {}
+    for recs in ([list(range(B))] if nbeam == 1 else [[b] for b in range(B)]):
+        outs.update(lf.run(feats, lens, recs))
+    L = max((len(o) for o in outs.values()), default=0)
     res = torch.full((B, L), pad, dtype=torch.int64)
-    for b, o in enumerate(outs):
+    for b, o in outs.items():
         res[b, :len(o)] = torch.tensor(o, dtype=torch.int64)
-    return res.to(dev)
+    return res.to(model.device)

@@ -4,7 +4,7 @@ The reference's long-form evaluation calls generate on a batch of recordings (`t
 inner_batch_size; large-v2 speed sweeps at --batch_size 128 .. 4 in `run-eval.sh:82-98`), and HF's sequential
 long-form keeps that batch together window after window (generation_whisper.py:785-898: each seek iteration cuts
 every unfinished recording's window at its own seek, encodes and decodes them as one batch; `_maybe_reduce_batch`
-drops finished recordings).  tw.generation._longform_batched does the same.
+drops finished recordings).  tw.generation._LongForm.run does the same.
 
 Fixture: tests/golden/batched_longform.npz (tests/golden/make_golden.py gen_batched_longform): ONE HF generate call
 on 3 recordings of 65 s, 41.3 s and 18.2 s (oracle/fixture_inputs.batched_longform_features, attention mask),

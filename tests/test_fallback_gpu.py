@@ -248,7 +248,7 @@ def test_batched_fallback_equals_sequential():
     """The speculative fallback batch (after a window's first attempt fails, the remaining temperatures decode
     together as one batch, one row per temperature with its own seed) gives exactly the attempts of decoding
     them one at a time: the same sampled tokens, the same per-attempt average log-prob and no-speech
-    probability, the same accepted attempt and output (tw/generation.py _longform)."""
+    probability, the same accepted attempt and output (tw/generation.py _LongForm.run)."""
     mg, cfg, w, m = _setup()
     lf = torch.from_numpy(mg.longform_features())
     kw = dict(attention_mask=torch.ones(1, lf.shape[-1], dtype=torch.long), return_timestamps=True, language="zh",
@@ -265,3 +265,27 @@ def test_batched_fallback_equals_sequential():
         assert strip(x["raw"]) == strip(y["raw"])
         assert x["avg_logprob"] == y["avg_logprob"] and x["no_speech_prob"] == y["no_speech_prob"]
         assert (x["needs_fallback"], x["skip"]) == (y["needs_fallback"], y["skip"])
+
+
+def test_one_conditioned_recording_bucketed_fallback_equals_sequential():
+    """One recording under condition_on_prev_tokens goes through the same seek loop as a batch of them, so its
+    fallback batch is rounded with _bucket: the five sampled temperatures decode as 8 rows (the three extra rows repeat
+    the first attempt and are dropped).  compression_ratio_threshold 0 fails every attempt, so every row of that batch
+    is compared with its own batch-1 decode (fallback_batch=False): the same output, per attempt the same seek,
+    temperature and prompt, the same tokens up to eos, and bit-equal average log-prob and no-speech probability."""
+    mg, cfg, w, m = _setup()
+    lf = torch.from_numpy(mg.longform_features())
+    kw = dict(attention_mask=torch.ones(1, lf.shape[-1], dtype=torch.long), return_timestamps=True, language="zh",
+              task="transcribe", condition_on_prev_tokens=True, temperature=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+              compression_ratio_threshold=0.0, max_new_tokens=40)
+    ta, tb = [], []
+    a = m.generate(lf, _trace=ta, fallback_batch=True, **kw).cpu()[0].tolist()
+    b = m.generate(lf, _trace=tb, fallback_batch=False, **kw).cpu()[0].tolist()
+    assert a == b
+    assert len(ta) == len(tb) and len(ta) % 6 == 0 and len(ta) >= 12
+    assert [t["batch"] for t in ta[:6]] == [1, 8, 8, 8, 8, 8] and all(t["batch"] == 1 for t in tb)
+    strip = lambda r: r[:next((i + 1 for i, x in enumerate(r) if x == 50257), len(r))]
+    for x, y in zip(ta, tb):
+        assert (x["seek"], x["T"], x["prompt"]) == (y["seek"], y["T"], y["prompt"])
+        assert strip(x["raw"]) == strip(y["raw"])
+        assert x["avg_logprob"] == y["avg_logprob"] and x["no_speech_prob"] == y["no_speech_prob"]

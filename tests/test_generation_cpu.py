@@ -25,12 +25,12 @@ class _ScriptedDecoder:
     decoder returns (DecodeSession ids are eos-filled, _Decoder.run trims at the last row's first eos)."""
     script = {}
 
-    def __init__(self, model, gc, nb, Tk, P, ml, timestamps, use_graph, track=False):
+    def __init__(self, model, gc, nb, Tk, P, ml, timestamps, use_graph, track=False, **kw):
         self.nb = nb
         self.sel = _Sel(nb)
         self.ns_logp = torch.zeros(nb)
 
-    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None):
+    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, **kw):
         # one encoder row per window here: nb rows (one per decode row), or one row shared by every decode row
         ids = enc16.flatten()
         wins = [int(ids[r].item()) if ids.numel() == self.nb else int(ids[0].item()) for r in range(self.nb)]

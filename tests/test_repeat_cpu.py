@@ -119,8 +119,8 @@ def test_unknown_keyword_still_raises_type_error():
 
 # ------------------------------------------------------------------------------------------ long-form plumbing
 def test_long_form_builds_its_decoders_with_the_options(monkeypatch):
-    """Every decoder of a long-form call (the window's and the fallback batch's) is built with the two options; with
-    both off the decoder is built by the call the parent made (no new argument)."""
+    """Every decoder of a long-form call (the window's and the fallback batch's) is built with the two options, passed
+    plainly; with both off they are (1.0, 0), the values with which _Select launches no pre-pass."""
     from test_generation_cpu import _ScriptedDecoder, _script
     from test_generation_cpu import _model as scripted_model
     built = []
@@ -142,7 +142,7 @@ def test_long_form_builds_its_decoders_with_the_options(monkeypatch):
     assert len(built) >= 2 and all(k == dict(repetition_penalty=1.3, no_repeat_ngram_size=2) for k in built)
     del built[:]
     off = generation.generate(m, feats, repetition_penalty=1.0, no_repeat_ngram_size=0, **common)
-    assert len(built) >= 2 and all(k == {} for k in built)
+    assert len(built) >= 2 and all(k == dict(repetition_penalty=1.0, no_repeat_ngram_size=0) for k in built)
     assert torch.equal(on, off)                                   # the scripted decoder ignores the options
 
 
