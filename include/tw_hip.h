@@ -400,8 +400,11 @@ int tw_gelu_bwd_f32(const float* g, const float* pre, float* out, int64_t n, tw_
  * v_mfma_f32_16x16x32_f16 with fp32 accumulation, every 16-bit operand / output IEEE fp16 (RNE).
  * tw_gemm_f16: tw_gemm_bf16 for fp16 operands (the decode path uses the forward products only);
  *   A, B, bias, aux fp16; C and res fp16 (code 2) or fp32; epilogue order as tw_gemm_bf16 with the rounding
- *   to fp16, plus TW_GEMM_CLAMP16: after the residual add, clamp to +-(65504 - 1000) (HF WhisperEncoderLayer,
- *   modeling_whisper.py:409-411, the fp16 encoder stream).
+ *   to fp16, plus TW_GEMM_CLAMP16: after the residual add and the ACCUM add (the last step before the store), the
+ *   value is rounded to fp16 and clamped to +-(65504 - 1000), so an overflow to +-inf lands on the bound too (HF
+ *   WhisperEncoderLayer, modeling_whisper.py:409-411, the fp16 encoder stream).  RES, ACCUM and CLAMP16 combine
+ *   with each other, and RES or ACCUM with DGELU, in that order on whole and on ragged tiles alike
+ *   (tests/test_gemm_parity_gpu.py; GELU followed by RES / ACCUM and DGELU with CLAMP16 are not under test).
  * tw_gemv_f16: tw_gemv_bf16 for fp16 x / W / bias / C (LayerNorm fused as there, fp16 output of the LN).
  * tw_attn_fwd_f16: tw_attn_fwd for fp16 Q/K/V/O (P rounded to fp16 for the PV product, fp32 row sums).
  * tw_mel_to_conv_input_f16: log-mel [B][80][T] fp32 -> fp16 conv1 input [B][T+2][80] (the .to(float16) cast).

@@ -166,7 +166,11 @@ __device__ __forceinline__ void epilogue_generic(const GemmP& p, const f32x4 (&a
   char* C = (char*)p.C;
   const bool full_tile = !RAGGED && (m0 + BM <= p.M) && (n0 + BN <= p.N) && ((p.ldc & 3) == 0) &&
                          (!(flags & F_RES) || ((p.ldr & 3) == 0 && p.res_mod == 0)) &&
-                         (!(flags & (F_AUX_OUT | F_DGELU)) || (p.ldaux & 3) == 0);
+                         (!(flags & (F_AUX_OUT | F_DGELU)) || (p.ldaux & 3) == 0) &&
+                         // the fast path loads ONE extra operand per element (`ex`: the DGELU pre-activation, else the
+                         // residual, else C_old); a call with two of them takes the per-element path below
+                         !((flags & F_RES) && (flags & F_ACCUM)) &&
+                         !((flags & F_DGELU) && (flags & (F_RES | F_ACCUM)));
   if (full_tile) {
     // fast path: no bounds checks, vector loads/stores, bias hoisted, loads of one fragment
     // row issued before any of its stores (C may alias res for in-place residual updates)

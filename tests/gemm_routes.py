@@ -240,6 +240,22 @@ def config_shapes():
     return sorted(s)
 
 
+PARITY_SHAPES = {
+    (1, 1, 8), (1, 17, 40), (1, 128, 200), (1, 129, 192), (5, 15, 40), (5, 51, 72), (5, 264, 72), (8, 128, 200),
+    (8, 129, 256), (8, 136, 256), (8, 255, 200), (16, 129, 256), (16, 136, 256), (32, 16, 72), (32, 16, 1280),
+    (32, 264, 1280), (33, 1, 8), (33, 17, 1280), (64, 15, 40), (64, 51, 8), (65, 16, 72), (65, 40, 264),
+    (65, 264, 40), (120, 248, 320), (120, 255, 320), (127, 248, 320), (127, 255, 320), (127, 256, 256),
+    (128, 1, 72), (128, 17, 1280), (128, 200, 1280), (128, 256, 8), (128, 257, 320), (129, 1, 8), (129, 136, 72),
+    (129, 257, 64), (129, 264, 64), (136, 129, 8), (136, 136, 1024), (136, 257, 64), (136, 264, 64), (136, 264, 72),
+    (200, 264, 2048), (248, 1, 72), (248, 8, 72), (255, 1, 72), (255, 8, 64), (255, 8, 72), (256, 8, 128),
+    (256, 16, 128), (256, 127, 72), (256, 129, 5120), (256, 136, 5120), (256, 136, 5128), (256, 256, 3072),
+    (256, 264, 3072), (256, 512, 128), (257, 120, 192), (257, 127, 192), (257, 128, 128), (257, 257, 128),
+    (257, 264, 128), (257, 264, 200), (264, 120, 192), (264, 127, 192), (264, 136, 5056), (264, 257, 128),
+    (264, 264, 72), (264, 264, 128), (300, 520, 3072), (512, 256, 128), (512, 256, 192), (512, 768, 3072),
+    (520, 392, 72), (520, 520, 72), (520, 520, 192), (776, 3080, 6144), (1280, 768, 64), (4096, 4096, 1024),
+    (4352, 4096, 64), (4352, 4096, 3072), (32868, 512, 64),
+}
+
 # every (M, N, K) of tests/test_kernels_gpu.py and tests/test_fp16_train_gpu.py (the dW tests' N, K, M as the product's
 # M, N, K = output rows, output columns, tokens)
 TEST_SHAPES = sorted({
@@ -251,7 +267,9 @@ TEST_SHAPES = sorted({
     (264, 136, 4096), (1280, 1280, 1000), (1, 16, 8), (5, 1000, 1280), (64, 1280, 5120), (100, 3840, 1280),
     (128, 200, 64), (128, 1280, 5120), (65, 520, 1280), (512, 1280, 1280), (300, 3840, 1280), (4096, 768, 768),
     (1024, 3072, 768), (28608, 5120, 1280), (28608, 51904, 1280), (1000, 2560, 1280), (1000, 1280, 256),
-    (768, 768, 14304), (768, 3072, 48000), (520, 520, 128)})
+    (768, 768, 14304), (768, 3072, 48000), (520, 520, 128)}
+    # ... and of the parity suite's case table (tests/gemm_cases.py; tests/test_gemm_cases_cpu.py checks the inclusion)
+    | PARITY_SHAPES)
 
 ROUTE_FLAGS = (0, TILE128, TILE256, TILE256x128, TILE256PP, TILE256x128_S2, NOSPLIT)
 

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+from gemm_cases import gelu_exact_bf16_bits as _gelu_exact_bf16_bits   # (the GEMM parity suite uses it too)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -121,27 +123,6 @@ def test_gemm_dgelu_fast_epilogue_bit_identical(M, N, K):
         ref = bf((bf((dy.double() @ W.double()).cpu().float()).double() * gp).float()).double()
         d = (fast.double().cpu() - ref).abs()
         assert not bool((d > 2 ** -7 * ref.abs() + 1e-30 + 1e-4 * ref.abs().max()).any()), float(d.max())
-
-
-def _gelu_exact_bf16_bits():
-    """bf16 bits of GELU for every bf16 bit pattern: PyTorch's erf-form formula in fp32 (reference),
-    x * 0.5 * (1 + erf(x * M_SQRT1_2)) (the reference's autocast F.gelu), with a correctly rounded
-    fp32 erf (math.erf in double, rounded once), then bf16 round-to-nearest-even;
-    +inf -> +inf, -inf -> -0, NaN -> NaN (the kernels' stated edge behaviour)."""
-    bits = np.arange(1 << 16, dtype=np.uint32)
-    with np.errstate(invalid="ignore"):
-        x = (bits << 16).view(np.float32).copy()
-        xa = x * np.float32(0.70710678118654752440)
-    fin = np.isfinite(x)
-    e = np.zeros_like(x)
-    e[fin] = np.array([math.erf(v) for v in xa[fin].astype(np.float64).tolist()]).astype(np.float32)
-    with np.errstate(invalid="ignore"):
-        g = (x * np.float32(0.5)) * (np.float32(1.0) + e)
-    out = torch.from_numpy(g).bfloat16().view(torch.int16).numpy().view(np.uint16).copy()
-    out[np.isposinf(x)] = 0x7f80
-    out[np.isneginf(x)] = 0x8000
-    out[np.isnan(x)] = 0x7fc0
-    return bits.astype(np.uint16), out
 
 
 def test_gemm_gelu_exhaustive():
