@@ -347,6 +347,25 @@ int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, in
 int tw_repeat_process(const void* logits, int64_t ld, int logits_dtype, int B, int V, const int64_t* ids,
                       int64_t ld_ids, int col, const int* t_dev, float penalty, int ngram, float* out, int64_t ld_out,
                       tw_stream_t stream);
+/* tw_lang_detect: HF WhisperGenerationMixin.detect_language on the logits of the <|startoftranscript|> step
+ * (generation_whisper.py: every non-language logit masked to -inf, argmax).  lang_ids: a device table of L language
+ * token ids (1 <= L <= 256), ascending and unique, each in [0, V).  The C entry cannot look into device memory: the
+ * table is checked on the host where it is built (tw/generation.py language_table); the kernel reads an id outside
+ * [0, V) as -inf rather than touching the row.  Per row b, in fp32 on the widened values x[j] = logits[b*ld +
+ * lang_ids[j]] (bf16, fp16 or fp32 in; columns [V, ld) are never read):
+ *   out_ids[b*id_stride] = lang_ids[argmax_j x[j]] with torch.argmax's rule: ties to the lowest id, a NaN above every
+ *     number and the lowest-id NaN first; a row whose language logits are all -inf gives the lowest language id (HF's
+ *     argmax over the whole masked row would give token 0 there: a difference no real checkpoint reaches, since its
+ *     logits are finite).  id_stride >= 1 in elements: 1 for a plain [B] vector, T for column c of a [B][T] id matrix
+ *     (out_ids pointing at that column); the other elements are not written.
+ *   out_probs (may be NULL) [B][ld_p], ld_p >= L: out_probs[b][j] = expf(x[j] - max) / sum_j expf(x[j] - max), the
+ *     softmax over the L language logits alone, in table order; a row that holds a NaN, or only -inf, gives NaN.
+ *     Columns [L, ld_p) are not written.
+ * One wave per row, every output element written once; no host read and no allocation (capturable in a graph).
+ * Returns 1 for B < 0, V <= 0, ld < V, L < 1, L > 256, id_stride < 1, ld_p < L with out_probs given, or a null
+ * logits / lang_ids / out_ids; 2 for another dtype; nothing is written then.  B == 0 is TW_OK with nothing launched. */
+int tw_lang_detect(const void* logits, int64_t ld, int logits_dtype, int B, int V, const int* lang_ids, int L,
+                   int64_t* out_ids, int64_t id_stride, float* out_probs, int64_t ld_p, tw_stream_t stream);
 int tw_embed_step(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
                   int out_dtype, int B, int D, const int* t_dev, tw_stream_t stream);
 /* tw_embed_step_off: out[b] = tok[ids[b]] + pos[max(*t_dev - pos_off[b], 0)] -- pos_off a device array of B int32,

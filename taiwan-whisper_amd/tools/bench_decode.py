@@ -4,6 +4,9 @@ synthetic 30 s features; eos is suppressed so every clip runs exactly --new-toke
 
     python tools/bench_decode.py [--batch 64] [--new-tokens 224] [--clips 128] [--eager] [--dtype float16]
                                  [--repetition_penalty 1.3] [--no_repeat_ngram_size 3]
+                                 [--language zh | auto | zh,en,...] [--runs 5] [--detect]
+--language auto detects every clip's language (generate(language="auto")); a comma list names one language per clip
+(repeated to the batch).  --runs N times N calls and prints each; --detect times detect_language alone instead.
 """
 import argparse
 import os
@@ -24,6 +27,9 @@ def main():
     ap.add_argument("--dtype", default="bfloat16", choices=["bfloat16", "float16"])
     ap.add_argument("--repetition_penalty", type=float, default=1.0)
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0)
+    ap.add_argument("--language", default="zh", help="a language, 'auto', or a comma list (one per clip, cycled)")
+    ap.add_argument("--runs", type=int, default=0, help="time this many single calls and print each (ms)")
+    ap.add_argument("--detect", action="store_true", help="time detect_language alone (with --runs)")
     ap.add_argument("--longform-seconds", type=float, default=0.0,
                     help="config c5: one input of this many seconds, return_timestamps, --new-tokens per window")
     a = ap.parse_args()
@@ -38,15 +44,22 @@ def main():
     random_init_(m, seed=0)
     m.generation_config = GenerationConfig(suppress_tokens=[50257], begin_suppress_tokens=[220, 50257],
                                            lang_to_id={"<|zh|>": 50260})
+    if a.language != "zh":      # large-v2's 99 language ids, so that detection has its real table
+        names = ["en", "zh"] + [f"l{i}" for i in range(2, 99)]
+        m.generation_config["lang_to_id"] = {f"<|{c}|>": 50259 + i for i, c in enumerate(names)}
+
+    def lang(n):
+        names = a.language.split(",")
+        return a.language if len(names) == 1 else [names[i % len(names)] for i in range(n)]
     if a.longform_seconds > 0:
         T = int(a.longform_seconds * 100)
         lf = torch.randn(1, 80, T, device="cuda") * 0.3
         trace = []
-        m.generate(lf[:, :, :3500], return_timestamps=True, language="zh", task="transcribe", max_new_tokens=8,
+        m.generate(lf[:, :, :3500], return_timestamps=True, language=lang(1), task="transcribe", max_new_tokens=8,
                    use_graph=not a.eager)                                                     # warm-up
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        out = m.generate(lf, return_timestamps=True, language="zh", task="transcribe", max_new_tokens=a.new_tokens,
+        out = m.generate(lf, return_timestamps=True, language=lang(1), task="transcribe", max_new_tokens=a.new_tokens,
                          use_graph=not a.eager, _trace=trace)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -57,12 +70,31 @@ def main():
         return
     rep = dict(repetition_penalty=a.repetition_penalty, no_repeat_ngram_size=a.no_repeat_ngram_size)
     feats = torch.randn(a.batch, 80, 3000, device="cuda") * 0.3
-    m.generate(feats[:2], language="zh", task="transcribe", max_new_tokens=4, use_graph=not a.eager, **rep)   # warm-up
+    m.generate(feats[:2], language=lang(2), task="transcribe", max_new_tokens=4, use_graph=not a.eager, **rep)  # warm-up
     torch.cuda.synchronize()
+    if a.runs > 0:
+        def one():
+            if a.detect:
+                return m.detect_language(feats)
+            return m.generate(feats, language=lang(a.batch), task="transcribe", max_new_tokens=a.new_tokens,
+                              use_graph=not a.eager, **rep)
+        one()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.runs):
+            t0 = time.perf_counter()
+            one()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+        what = "detect_language" if a.detect else f"generate language={a.language} {a.new_tokens} tokens"
+        per = "" if a.detect else f", median {sorted(ms)[len(ms) // 2] / a.new_tokens:.3f} ms/step"
+        print(f"{what} {a.config} {a.dtype} batch {a.batch}: per call ms {' '.join(f'{x:.2f}' for x in ms)} "
+              f"(min {min(ms):.2f}, median {sorted(ms)[len(ms) // 2]:.2f}, max {max(ms):.2f}{per})", flush=True)
+        return
     n_sub = max(1, a.clips // a.batch)
     t0 = time.perf_counter()
     for _ in range(n_sub):
-        out = m.generate(feats, language="zh", task="transcribe", max_new_tokens=a.new_tokens,
+        out = m.generate(feats, language=lang(a.batch), task="transcribe", max_new_tokens=a.new_tokens,
                          use_graph=not a.eager, **rep)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0

@@ -74,6 +74,7 @@ SIGNATURES = {
     "tw_select_sample_ts": [P, I64, I32, I32, I32, P, P, I64, P, P, I64, I32, P, P, I32, I32, I32, I32, P, P, P, P],
     "tw_token_logprob": [P, I64, I32, I32, I32, I32, P, P],
     "tw_repeat_process": [P, I64, I32, I32, I32, P, I64, I32, P, F32, I32, P, I64, P],
+    "tw_lang_detect": [P, I64, I32, I32, I32, P, I32, P, I64, P, I64, P],
     "tw_embed_step": [P, P, I32, P, I32, P, I32, I32, I32, P, P],
     "tw_kv_append": [P, I64, P, I64, I64, I32, I32, I32, P, P],
     "tw_kv_head_major": [P, I64, P, I32, I32, I32, I32, P],

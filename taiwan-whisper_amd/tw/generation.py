@@ -306,17 +306,121 @@ def _lang_id(gc, language):
     raise ValueError(f"unknown language {language!r} (generation_config.lang_to_id has {sorted(l2i)[:5]}...)")
 
 
-def build_prompt(gc, language=None, task=None, return_timestamps=False):
-    """HF Whisper prompt: [SOT, <|lang|>, <|task|>, (<|notimestamps|>)] (generation_whisper.py)."""
+def build_prompt(gc, language=None, task=None, return_timestamps=False, detected=False):
+    """HF Whisper prompt: [SOT, <|lang|>, <|task|>, (<|notimestamps|>)] (generation_whisper.py).  detected: the
+    language comes from detection, not from the caller; HF then adds a task token only for a task that was passed
+    (_retrieve_init_tokens defaults to <|transcribe|> only `elif language is not None`)."""
     ids = [gc.decoder_start_token_id]
     lid = _lang_id(gc, language)
     if lid is not None:
         ids.append(lid)
-    if task is not None or lid is not None:
+    if task is not None or (lid is not None and not detected):
         ids.append(dict(gc.task_to_id or {}).get(task or "transcribe", 50359))
     if not return_timestamps:
         ids.append(gc.no_timestamps_token_id)
     return ids
+
+
+AUTO = "auto"          # generate(language="auto"): HF's language=None, detection per row
+
+
+def language_table(gc, V):
+    """The ids tw_lang_detect chooses among: sorted(generation_config.lang_to_id.values()), checked here because the
+    kernel's C entry cannot look into device memory -- unique (ascending once sorted), inside [0, V), at most
+    ops.LANG_MAX.  An empty or missing lang_to_id raises ValueError."""
+    l2i = gc.get("lang_to_id") if hasattr(gc, "get") else getattr(gc, "lang_to_id", None)
+    if not l2i:
+        raise ValueError("tw: language detection needs generation_config.lang_to_id (the generation config names no "
+                         "language tokens)")
+    ids = sorted(int(v) for v in dict(l2i).values())
+    if len(set(ids)) != len(ids) or ids[0] < 0 or ids[-1] >= V or len(ids) > F.LANG_MAX:
+        raise ValueError(f"tw: generation_config.lang_to_id must hold 1..{F.LANG_MAX} distinct ids in [0, {V}); got "
+                         f"{len(ids)} ids from {ids[0]} to {ids[-1]}")
+    return ids
+
+
+def language_rows(gc, language, B):
+    """generate's `language` -> None (no language token), AUTO, or one language id per row.  A list or tuple names
+    one language per row, each whatever a single `language` may be; HF's errors (_retrieve_init_tokens): TypeError
+    for a None element, ValueError for a length other than the batch size."""
+    if isinstance(language, (list, tuple)):
+        if any(l is None for l in language):
+            raise TypeError("Expected `language` to be `None`, a single string (e.g. `'en'`), or a list of strings "
+                            "with length equal to the batch size (e.g. `('en', 'fr')` for a batch size of 2). Got a "
+                            "list containing `None`.")
+        if len(language) != B:
+            raise ValueError("When passing a list of languages, the length of the list must match the batch size. "
+                             f"Expected length of {B}, but got {len(language)} languages.")
+        return [_lang_id(gc, l) for l in language]
+    if isinstance(language, str) and language == AUTO:
+        return AUTO
+    lid = _lang_id(gc, language)
+    return None if lid is None else [lid] * B
+
+
+def _detect(model, gc, enc16, B, Tk, want_probs=False):
+    """HF detect_language's decoder part on B clips' encoder rows: one step at position 0 on <|startoftranscript|>
+    through a DecodeSession, then tw_lang_detect over the language ids -> (ids int64 [B], probs fp32 [B, L] or None,
+    the id table)."""
+    table = language_table(gc, model.config.vocab_size)
+    dev = model.device
+    sess = DecodeSession(model, enc16, B, Tk, 2)          # position 0 and a spare cache row
+    sess.cur.fill_(int(gc.decoder_start_token_id))
+    sess.step()
+    ids = torch.empty(B, dtype=torch.int64, device=dev)
+    probs = torch.empty(B, len(table), dtype=torch.float32, device=dev) if want_probs else None
+    F.lang_detect(sess.logits, model.Vp, B, model.config.vocab_size, torch.tensor(table, dtype=torch.int32, device=dev),
+                  ids, probs)
+    return ids, probs, table
+
+
+def _first_window(model, input_features):
+    """HF's input_features[:, :, :3000]: the first 30 s of every input, zero-padded on the right when shorter."""
+    window = 2 * model.config.max_source_positions
+    f = input_features[:, :, :window]
+    if f.shape[-1] < window:
+        f = torch.nn.functional.pad(f, (0, window - f.shape[-1]))
+    return f
+
+
+def _resolve_gc(model):
+    from .config import GenerationConfig
+    gc = model.generation_config if model.generation_config is not None else GenerationConfig()
+    if not isinstance(gc, GenerationConfig):
+        gc = GenerationConfig(gc)
+    if gc.eos_token_id is None:
+        gc.eos_token_id = model.config.eos_token_id
+    return gc
+
+
+@torch.no_grad()
+def detect_language(model, input_features=None, encoder_outputs=None, return_probs=False):
+    """HF WhisperGenerationMixin.detect_language (transformers 5.15 generation_whisper.py:1610-1673): the language
+    token id of each input, int64 [B] on the device -- the largest of the language logits at the position after
+    <|startoftranscript|>.  Exactly one of input_features (cut to the first 3000 frames, zero-padded when shorter)
+    and encoder_outputs.  return_probs=True: (ids, probs fp32 [B, L], ids_table) with probs[b, j] the softmax over
+    the L = len(lang_to_id) language logits alone of language ids_table[j] (sorted ids); HF has no such output,
+    faster-whisper's language_probability is this number.  Ties go to the lowest id, as torch.argmax; a row whose
+    language logits are all -inf gives the lowest language id where HF gives token 0 (unreachable: logits are
+    finite)."""
+    if input_features is None and encoder_outputs is None:
+        raise ValueError("You have to specify either `input_features` or `encoder_outputs`")
+    if input_features is not None and encoder_outputs is not None:
+        raise ValueError("Make sure to specify only one of `input_features` or `encoder_outputs` - not both!")
+    gc = _resolve_gc(model)
+    language_table(gc, model.config.vocab_size)
+    cfg = model.config
+    if encoder_outputs is not None:
+        enc = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
+        B, Tk = enc.shape[0], enc.shape[1]
+        enc16 = enc.reshape(-1, cfg.d_model).to(model.device, model.act_dtype).contiguous()
+    else:
+        conv_in = model.conv_input(_first_window(model, input_features))
+        enc16 = model.encode(conv_in)
+        B = conv_in.shape[0]
+        Tk = enc16.shape[0] // B
+    ids, probs, table = _detect(model, gc, enc16, B, Tk, return_probs)
+    return (ids, probs, table) if return_probs else ids
 
 
 class _Select:
@@ -408,9 +512,13 @@ class _PromptedDecode:
         """log-softmax of the raw logits at no_speech's token -> ns_logp (WhisperNoSpeechDetection)."""
         F.token_logprob(logits, self.m.Vp, self.B, self.m.config.vocab_size, no_speech[1], self.ns_logp)
 
-    def _prefill(self, sessions, no_speech):
+    def _prefill(self, sessions, no_speech, detect=None):
         """Prompt columns 0 .. P - 2 through every session, from position 0; the first session is the one whose
-        logits at the <|startoftranscript|> position the no-speech probe reads."""
+        logits at the <|startoftranscript|> position the no-speech probe reads.
+        detect (a device int32 table of language ids, language_table): the step at column 0 is HF's detection step,
+        so tw_lang_detect writes each row's language id from the first session's logits into column 1 of the id
+        matrix, on the device, before the prefill reads that column (the prompt holds a placeholder there; column 0
+        must be <|startoftranscript|>, i.e. no prompt_ids)."""
         for sess in sessions:
             sess.t_dev.zero_()
         for t in range(self.P - 1):
@@ -419,6 +527,9 @@ class _PromptedDecode:
                 sess.step()
                 if sess is sessions[0] and no_speech is not None and t == no_speech[0]:
                     self._probe(sess.logits, no_speech)
+                if sess is sessions[0] and detect is not None and t == 0:
+                    F.lang_detect(sess.logits, self.m.Vp, self.B, self.m.config.vocab_size, detect,
+                                  self.sel.ids[:, 1])
 
     def _trim(self, t):
         """The generated columns up to t without the trailing ones in which every row had already finished (HF stops
@@ -444,8 +555,11 @@ class _Decoder(_PromptedDecode):
         self.B, self.Tk = B, Tk
         self.ns_logp = torch.zeros(B, dtype=torch.float32, device=model.device) if track else None
 
-    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False):
+    def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False,
+            detect=None):
         """prompt: int64 [B, P] (device) -> generated ids [B, L] (device), HF trimming.
+        detect: the device table of language ids -> the languages are detected inside the prefill (_prefill) and
+        sel.ids[:, 1] holds them afterwards; `prompt` carries any valid language id there.
         pads: per-row count of leading pad columns of `prompt` (rows left-padded to the longest prompt of the batch,
         as HF pads them): those columns are masked from the row's self-attention; every row embeds at its column
         index, as HF does.  shift_positions=True instead counts a row's positions from its first real token, so that
@@ -456,7 +570,8 @@ class _Decoder(_PromptedDecode):
         sess = self.sess = self._open(self.sess, self.m, enc16, self.Tk)
         sess.set_pads(pads, shift_positions)
         sel.reset(prompt, temperature, seed)
-        self._prefill([sess], no_speech)
+        assert detect is None or (P >= 2 and pads is None)
+        self._prefill([sess], no_speech, detect)
         sess.cur.copy_(sel.ids[:, P - 1])
         if self.use_graph and sess.graph is None:
             sess.capture(sel)
@@ -853,7 +968,7 @@ def _repeat_names(penalty, ngram):
 def generate(model, input_features=None, max_length=None, num_beams=1, return_timestamps=False, language=None,
              task=None, decoder_input_ids=None, max_new_tokens=None, encoder_outputs=None, attention_mask=None,
              use_graph=None, prompt_ids=None, prompt_condition_type=None, assistant_model=None,
-             num_assistant_tokens=None, **kw):
+             num_assistant_tokens=None, return_language=False, **kw):
     """HF WhisperGenerationMixin.generate (transformers 5.15 generation_whisper.py), the calls the reference makes.
     prompt_ids (run_eval.py:656-657 --prompt_text): 1-D ids from get_prompt_ids (<|startofprev|> + text), placed in
     front of the task prompt of every decoded window (_prepare_decoder_input_ids; with the default
@@ -871,8 +986,20 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     before the suppress / timestamp rules, the log-prob of the fallback gate and sampling; the history is the whole
     decoder row (left padding, <|startofprev|> text and task prompt included).  Defaults come from generation_config
     when it names them.  Greedy and long-form (fallback, condition_on_prev_tokens) decoding take them; beam search and
-    assisted decoding raise NotImplementedError.  Any keyword that is not implemented raises TypeError."""
-    from .config import GenerationConfig
+    assisted decoding raise NotImplementedError.  Any keyword that is not implemented raises TypeError.
+    language: None -- no language token in the prompt (NOT HF's meaning: HF's language=None detects; here that is
+    language="auto"); a name, code, token or id for every row; a list / tuple with one of those per row (HF's
+    language=[...]; a length other than the batch size is HF's ValueError, a None element HF's TypeError);
+    "auto" -- every row's language is detected as HF detect_language does (the largest language logit after
+    <|startoftranscript|> on the first 30 s) and, as in HF, no task token follows unless `task` is passed.
+    "auto" needs generation_config.lang_to_id and excludes decoder_input_ids (ValueError).  Short-form greedy
+    decoding without prompt_ids detects inside the prompt prefill, on the device (_PromptedDecode._prefill: no
+    second pass, no host read); every other form -- prompt_ids, beam search, assisted and long-form decoding, the
+    latter once per call on each recording's first 3000 raw frames -- runs detect_language's step first and reads
+    the B ids back.  Beam search decodes one prompt, so rows of different languages raise NotImplementedError.
+    return_language=True returns (ids, language ids int64 [B] on the device) for any language form but None (there is
+    no language to return: ValueError).  With decoder_input_ids the caller owns the prompt: `language` is not looked
+    at, as before, and return_language raises ValueError."""
     unknown = sorted(set(kw) - GENERATE_KEYWORDS)
     if unknown:
         raise TypeError(f"tw generate: unsupported keyword argument(s) {', '.join(unknown)}")
@@ -901,11 +1028,7 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
               compression_ratio_threshold=kw.get("compression_ratio_threshold"),
               logprob_threshold=kw.get("logprob_threshold"), no_speech_threshold=kw.get("no_speech_threshold"),
               condition_on_prev_tokens=bool(kw.get("condition_on_prev_tokens") or False), seed=int(kw.get("seed", 0)))
-    gc = model.generation_config if model.generation_config is not None else GenerationConfig()
-    if not isinstance(gc, GenerationConfig):
-        gc = GenerationConfig(gc)
-    if gc.eos_token_id is None:
-        gc.eos_token_id = model.config.eos_token_id
+    gc = _resolve_gc(model)
     cfg = model.config
     penalty, ngram = repeat_options(gc, kw)
     if penalty != 1.0 or ngram > 0:
@@ -917,6 +1040,29 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if assist is not None:
             raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with assisted decoding "
                                       "(assistant_model) is not implemented")
+    if encoder_outputs is not None:
+        e0 = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
+        rows_in = e0.shape[0]
+    else:
+        rows_in = input_features.shape[0] if input_features is not None else 0
+    # the new forms ("auto", one language per row) are resolved here, so that their errors come before any device
+    # work; a single language is resolved where the prompt is built, as before (with decoder_input_ids it is not
+    # looked at)
+    per_row = isinstance(language, (list, tuple)) or (isinstance(language, str) and language == AUTO)
+    langs = language_rows(gc, language, rows_in) if per_row else None
+    if langs == AUTO:
+        if decoder_input_ids is not None:
+            raise ValueError("tw generate: language='auto' builds the prompt around the detected language; with "
+                             "decoder_input_ids the caller owns the prompt")
+        language_table(gc, cfg.vocab_size)
+    if return_language and language is None:
+        raise ValueError("tw generate: return_language=True needs a language (a name, a list, or 'auto')")
+    if return_language and decoder_input_ids is not None:
+        raise ValueError("tw generate: return_language=True with decoder_input_ids: the caller owns the prompt, and "
+                         "`language` is not looked at")
+    if nb > 1 and langs not in (None, AUTO) and len(set(langs)) > 1:
+        raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the rows of this call "
+                                  "name different languages")
     use_graph = True if use_graph is None else use_graph
     window = 2 * cfg.max_source_positions                     # 3000 feature frames = 30 s
     # HF (generation_whisper.py:785-898) runs the seek loop for every input when timestamps are predicted, a
@@ -927,7 +1073,7 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         return _longform(model, gc, input_features, attention_mask, language, task, max_length, max_new_tokens,
                          use_graph, window, kw.get("_trace"), fallback_batch=bool(kw.get("fallback_batch", True)),
                          num_beams=nb, prompt_ids=prompt_ids, assist=assist, repetition_penalty=penalty,
-                         no_repeat_ngram_size=ngram, **fb)
+                         no_repeat_ngram_size=ngram, return_language=bool(return_language), **fb)
     if kw.get("do_sample") or fb["temperature"] not in (0, 0.0) or fb["logprob_threshold"] is not None \
             or fb["compression_ratio_threshold"] is not None or fb["no_speech_threshold"] is not None:
         # the reference applies fallback / thresholds to long-form inputs only (run_eval.py:659-685)
@@ -942,17 +1088,44 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         enc16 = model.encode(conv_in)
         B = conv_in.shape[0]
         Tk = enc16.shape[0] // B
+    detect = lang_out = None
     if decoder_input_ids is not None:
         prompt = torch.as_tensor(decoder_input_ids, dtype=torch.int64)
         if prompt.dim() == 1:
             prompt = prompt[None].repeat(B, 1)
-    else:
+    elif langs is None:                      # one language (or none) for every row: the prompt of before
         prompt = torch.tensor((prompt_ids or []) + build_prompt(gc, language, task, return_timestamps),
                               dtype=torch.int64)[None].repeat(B, 1)
+        if return_language:
+            lang_out = torch.full((B,), _lang_id(gc, language), dtype=torch.int64, device=model.device)
+    else:
+        auto = langs == AUTO
+        if auto and nb == 1 and assist is None and not prompt_ids:
+            # the prefill's step at column 0 is the detection step: column 1 holds a placeholder until then
+            table = language_table(gc, cfg.vocab_size)
+            detect = torch.tensor(table, dtype=torch.int32, device=model.device)
+            langs = [table[0]] * B
+        elif auto:
+            # <|startoftranscript|> is not at position 0 (prompt_ids), or the decoder takes host prompts: a pass of
+            # its own over the same encoder rows, one readback of B ids
+            langs = _detect(model, gc, enc16, B, Tk)[0].tolist()
+            if nb > 1 and len(set(langs)) > 1:
+                raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the rows of "
+                                          f"this call were detected as different languages ({langs})")
+        prompt = torch.tensor([(prompt_ids or []) + build_prompt(gc, lid, task, return_timestamps, detected=auto)
+                               for lid in langs], dtype=torch.int64)
+        lang_out = torch.tensor(langs, dtype=torch.int64, device=model.device)
+
+    def result(out, dec=None):
+        if not return_language:
+            return out
+        return out, (dec.sel.ids[:, 1].clone() if detect is not None else lang_out)
     P = prompt.shape[1]
     max_length = total_length(cfg, gc, P, max_length, max_new_tokens)
     if P >= max_length:
-        return torch.empty(B, 0, dtype=torch.int64, device=model.device)
+        if return_language and detect is not None:
+            lang_out, detect = _detect(model, gc, enc16, B, Tk)[0], None
+        return result(torch.empty(B, 0, dtype=torch.int64, device=model.device))
     if assist is not None:
         if B != 1:
             raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
@@ -963,16 +1136,18 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         out = dec.run(enc16, prompt.to(model.device), enc_a=enc_a)
         if kw.get("_trace") is not None:
             kw["_trace"].append(dict(accepted=list(dec.accepted), num_assistant_tokens=dec.k))
-        return out
+        return result(out)
     if nb > 1:
         if not bool((prompt == prompt[:1]).all()):
             raise NotImplementedError("tw generate: beam search takes one prompt for every clip")
-        return _BeamDecoder(model, gc, B, nb, Tk, P, max_length).run(enc16, prompt[0])
+        return result(_BeamDecoder(model, gc, B, nb, Tk, P, max_length).run(enc16, prompt[0]))
     dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph, repetition_penalty=penalty,
                    no_repeat_ngram_size=ngram)
     if kw.get("_keep") is not None:          # tests: the decoder (and its device caches) outlive the call
         kw["_keep"].append(dec)
-    return dec.run(enc16, prompt.to(model.device))
+    if detect is None:
+        return result(dec.run(enc16, prompt.to(model.device)))
+    return result(dec.run(enc16, prompt.to(model.device), detect=detect), dec)
 
 
 _ASSIST_GC_KEYS = ("eos_token_id", "pad_token_id", "decoder_start_token_id", "suppress_tokens", "begin_suppress_tokens",
@@ -1082,19 +1257,22 @@ def previous_text(segments, ts_begin):
     return prev
 
 
-def conditioned_prompts(init, segments, cond_on, conditioned, prev_sot, cut_off, ts_begin):
+def conditioned_prompts(init, segments, cond_on, conditioned, prev_sot, cut_off, ts_begin, inits=None):
     """The decoder prompts of one seek iteration of the batched long-form loop (HF _prepare_decoder_input_ids):
     segments / cond_on hold, per active row, its accepted segments and whether it conditions on them.  Not
     `conditioned`: every row takes init.  Otherwise row r takes <|startofprev|> (prev_sot, when the model has one) +
     the last cut_off tokens of its previous text (only when cond_on[r] and it has segments) + init.
+    inits: one init per row in place of `init` (rows of different languages: equal lengths, another language token).
     -> (unpadded prompts, the length they are left-padded to)."""
+    inits = [init] * len(segments) if inits is None else inits
+    assert len(inits) == len(segments) and len({len(i) for i in inits}) <= 1
     if not conditioned:
-        return [list(init) for _ in segments], len(init)
+        return [list(i) for i in inits], len(inits[0]) if inits else len(init)
     head = [int(prev_sot)] if prev_sot is not None else []
     out = []
-    for sg, on in zip(segments, cond_on):
+    for sg, on, ini in zip(segments, cond_on, inits):
         prev = previous_text(sg, ts_begin)[-cut_off:] if on and sg else []
-        out.append(head + prev + list(init))
+        out.append(head + prev + list(ini))
     return out, max(len(p) for p in out)
 
 
@@ -1131,7 +1309,8 @@ class _LongForm:
     transformers 5.15 does, so a padded row is HF's row, not the decode of its unpadded prompt.  As in HF, the
     conditioned form starts once the group's first recording has a segment, and from then on a row without previous
     text carries <|startofprev|> alone (no <|startofprev|> id: the rows condition without it).
-    init: prompt_ids + task prompt, the unconditioned prompt; n_task: the length of its task part.  assist =
+    init: per recording of the call, prompt_ids + task prompt, the unconditioned prompt (the recordings' language
+    tokens may differ, the lengths do not); n_task: the length of its task part.  assist =
     (assistant, k), one recording: the temperature-0 attempt of each window is assisted (_SpecDecoder)."""
     model: object
     gc: object
@@ -1252,9 +1431,9 @@ class _LongForm:
             if not active:
                 break
             nfr = {b: min(window, int(lens[b]) - seek[b]) for b in active}
-            prompts, P = conditioned_prompts(self.init, [segments[b] for b in active], [cond_on[b] for b in active],
+            prompts, P = conditioned_prompts(None, [segments[b] for b in active], [cond_on[b] for b in active],
                                              any(cond_on.values()) and len(segments[recs[0]]) > 0, self.prev_sot,
-                                             self.cut_off, self.ts_begin)
+                                             self.cut_off, self.ts_begin, inits=[self.init[b] for b in active])
             ml = total_length(model.config, self.gc, P, self.max_length, self.max_new_tokens)
             if P >= ml:
                 raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
@@ -1335,7 +1514,7 @@ class _LongForm:
 def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
               trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
               no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
-              prompt_ids=None, assist=None, repetition_penalty=1.0, no_repeat_ngram_size=0):
+              prompt_ids=None, assist=None, repetition_penalty=1.0, no_repeat_ngram_size=0, return_language=False):
     """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from `seek`, decoded
     with the timestamp rules and HF's temperature fallback; trailing eos/pad trimmed, segments split at consecutive
     timestamps, seek advanced by the last timestamp (or the whole window on a single-timestamp ending).  Returns the
@@ -1344,12 +1523,33 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     One seek loop (_LongForm.run) serves every form.  num_beams == 1: the recordings of the call are one group and
     decode as one batch.  num_beams > 1 (run_eval.py --num_beams with timestamps / long-form): every recording is a
     group of its own, in recording order, so each window is encoded alone (the encoder's output depends on the batch
-    it runs in); a temperature-0 attempt is a beam search over the window, a sampled attempt keeps one beam."""
+    it runs in); a temperature-0 attempt is a beam search over the window, a sampled attempt keeps one beam.
+    language: what generate takes.  A list, or "auto", gives every recording its own task prompt for all of its
+    windows; "auto" detects once per call, as HF does, on the first 3000 raw frames of every recording (HF's
+    input_features[:, :, :3000], not the zero-filled window the seek loop cuts), enc_rows recordings at a time.
+    return_language: -> (ids, language ids int64 [B])."""
     cfg = model.config
     feats = feats.to(model.device, torch.float32)
     B, _, T = feats.shape
     lens = attention_mask.sum(-1).tolist() if attention_mask is not None else [T] * B
-    task_init = build_prompt(gc, language, task, True)
+    nbeam = max(1, int(num_beams or 1))
+    langs = language_rows(gc, language, B)
+    if return_language and langs is None:
+        raise ValueError("tw generate: return_language=True needs a language (a name, a list, or 'auto')")
+    auto = langs == AUTO
+    if auto:
+        language_table(gc, cfg.vocab_size)
+        langs = []
+        for c0 in range(0, B, _LongForm.enc_rows):
+            e = model.encode(model.conv_input(_first_window(model, feats[c0:c0 + _LongForm.enc_rows])))
+            n = min(B, c0 + _LongForm.enc_rows) - c0
+            langs += _detect(model, gc, e, n, e.shape[0] // n)[0].tolist()
+            del e
+    if nbeam > 1 and langs is not None and len(set(langs)) > 1:
+        raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the recordings of this "
+                                  f"call have different languages ({langs})")
+    task_inits = [build_prompt(gc, lid, task, True, detected=auto) for lid in (langs if langs is not None else [None])]
+    task_init = task_inits[0] if task_inits else build_prompt(gc, None, task, True)
     temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (temperature,)
     track = (logprob_threshold is not None or no_speech_threshold is not None or any(t and t > 0 for t in temps)
              or len(temps) > 1)
@@ -1358,14 +1558,14 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     if prev_sot is None:
         sup = list(gc.suppress_tokens or [])
         prev_sot = sup[-2] if len(sup) >= 2 else None
-    nbeam = max(1, int(num_beams or 1))
     lf = _LongForm(model=model, gc=gc, temps=temps, track=track, window=window,
                    compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
                    no_speech_threshold=no_speech_threshold, fallback_batch=fallback_batch,
                    cond=bool(condition_on_prev_tokens), eos=eos, pad=pad, ts_begin=int(gc.no_timestamps_token_id) + 1,
                    ns_token=int(gc.no_timestamps_token_id) - 1, prev_sot=prev_sot,
                    cut_off=cfg.max_target_positions // 2 - 1,
-                   init=list(prompt_ids or []) + task_init,    # prompt_ids: in front of every window's task prompt
+                   # prompt_ids: in front of every window's task prompt
+                   init=[list(prompt_ids or []) + (task_inits[b] if langs is not None else task_init) for b in range(B)],
                    n_task=len(task_init), max_length=max_length, max_new_tokens=max_new_tokens, use_graph=use_graph,
                    assist=assist, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                    num_beams=nbeam, seed=seed, trace=trace)
@@ -1376,4 +1576,6 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     res = torch.full((B, L), pad, dtype=torch.int64)
     for b, o in outs.items():
         res[b, :len(o)] = torch.tensor(o, dtype=torch.int64)
+    if return_language:
+        return res.to(model.device), torch.tensor(langs, dtype=torch.int64, device=model.device)
     return res.to(model.device)

@@ -768,6 +768,11 @@ class WhisperForConditionalGeneration:
         from .generation import generate
         return generate(self, input_features, **kw)
 
+    def detect_language(self, input_features=None, encoder_outputs=None, return_probs=False):
+        """HF WhisperGenerationMixin.detect_language: the language token id of each input (tw/generation.py)."""
+        from .generation import detect_language
+        return detect_language(self, input_features, encoder_outputs, return_probs)
+
 
 class WhisperForCausalLM(WhisperForConditionalGeneration):
     """The decoder of a distilled student used as the assistant of assisted decoding over the TARGET's encoder output

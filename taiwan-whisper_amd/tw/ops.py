@@ -720,6 +720,38 @@ def token_logprob(logits, ld, B, V, token, out):
     return out
 
 
+LANG_MAX = 256         # tw_lang_detect's table bound
+
+
+def lang_detect(logits, ld, B, V, table, out_ids, out_probs=None):
+    """Language detection on B logits rows (tw_lang_detect): out_ids[b] = the id of `table` (int32, device, ascending
+    and unique, in [0, V): checked where it is built) whose logit is largest, torch.argmax's ties; out_probs[b, :L] =
+    softmax over the L table logits (float32).  out_ids: an int64 vector of B elements with any element stride, e.g.
+    column 1 of a [B, T] id matrix, whose other elements are left alone."""
+    L = table.numel()
+    assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32)
+    assert table.dtype == torch.int32 and table.is_contiguous() and table.device == logits.device
+    assert out_ids.dtype == torch.int64 and out_ids.dim() == 1 and out_ids.shape[0] == B
+    if not 1 <= L <= LANG_MAX:
+        raise ValueError(f"tw: lang_detect takes 1..{LANG_MAX} language ids, got {L}")
+    if B == 0:
+        return out_ids
+    _need(logits, (B - 1) * ld + V, "lang_detect logits")
+    _need(table, L, "lang_detect table")
+    stride = out_ids.stride(0) if B > 1 else 1
+    _need(out_ids, (B - 1) * stride + 1, "lang_detect out_ids")
+    ld_p = 0
+    if out_probs is not None:
+        assert out_probs.dtype == torch.float32 and out_probs.dim() == 2 and out_probs.stride(1) == 1
+        if out_probs.shape[0] < B or out_probs.shape[1] < L:
+            raise ValueError(f"tw: lang_detect out_probs {tuple(out_probs.shape)} holds no [{B}, {L}]")
+        ld_p = out_probs.stride(0) if B > 1 else out_probs.shape[1]
+        _need(out_probs, (B - 1) * ld_p + L, "lang_detect out_probs")
+    call("tw_lang_detect", logits.data_ptr(), ld, _dt(logits), B, V, table.data_ptr(), L, out_ids.data_ptr(), stride,
+         _ptr(out_probs), ld_p, _stream())
+    return out_ids
+
+
 def sample_ctl(temperature, seed, out=None):
     """Device control words of select_sample[_ts], one per row: [bits(1/T) (0 = greedy), seed lo, seed hi] x B.
     temperature / seed: scalars (one row) or equal-length sequences (a batch of independent attempts)."""
