@@ -32,6 +32,11 @@ import types
 import torch
 
 from . import ops as F
+# the request planner and the pure host helpers; imported by name so that they stay reachable as generation.<name>
+from .generate_plan import (ASSISTED, AUTO, BEAM, DEFAULT_ASSISTANT_TOKENS, GENERATE_KEYWORDS,  # noqa: F401
+                            MAX_ASSISTANT_TOKENS, OWN_PASS, PREFILL, Request, _ASSIST_GC_KEYS, _lang_id, _repeat_names,
+                            build_prompt, check_assistant, gc_get, language_rows, language_table, plan_generate,
+                            repeat_options, total_length)
 
 
 class _StepBufs:
@@ -290,74 +295,6 @@ class DecodeSession:
         self.graph = g
 
 
-def _lang_id(gc, language):
-    if language is None:
-        return None
-    if isinstance(language, int):
-        return language
-    l2i = dict(gc.lang_to_id or {})
-    for key in (language, f"<|{language}|>"):
-        if key in l2i:
-            return l2i[key]
-    builtin = {"en": 50259, "zh": 50260}
-    lang = language.strip("<|>")
-    if lang in builtin:
-        return builtin[lang]
-    raise ValueError(f"unknown language {language!r} (generation_config.lang_to_id has {sorted(l2i)[:5]}...)")
-
-
-def build_prompt(gc, language=None, task=None, return_timestamps=False, detected=False):
-    """HF Whisper prompt: [SOT, <|lang|>, <|task|>, (<|notimestamps|>)] (generation_whisper.py).  detected: the
-    language comes from detection, not from the caller; HF then adds a task token only for a task that was passed
-    (_retrieve_init_tokens defaults to <|transcribe|> only `elif language is not None`)."""
-    ids = [gc.decoder_start_token_id]
-    lid = _lang_id(gc, language)
-    if lid is not None:
-        ids.append(lid)
-    if task is not None or (lid is not None and not detected):
-        ids.append(dict(gc.task_to_id or {}).get(task or "transcribe", 50359))
-    if not return_timestamps:
-        ids.append(gc.no_timestamps_token_id)
-    return ids
-
-
-AUTO = "auto"          # generate(language="auto"): HF's language=None, detection per row
-
-
-def language_table(gc, V):
-    """The ids tw_lang_detect chooses among: sorted(generation_config.lang_to_id.values()), checked here because the
-    kernel's C entry cannot look into device memory -- unique (ascending once sorted), inside [0, V), at most
-    ops.LANG_MAX.  An empty or missing lang_to_id raises ValueError."""
-    l2i = gc.get("lang_to_id") if hasattr(gc, "get") else getattr(gc, "lang_to_id", None)
-    if not l2i:
-        raise ValueError("tw: language detection needs generation_config.lang_to_id (the generation config names no "
-                         "language tokens)")
-    ids = sorted(int(v) for v in dict(l2i).values())
-    if len(set(ids)) != len(ids) or ids[0] < 0 or ids[-1] >= V or len(ids) > F.LANG_MAX:
-        raise ValueError(f"tw: generation_config.lang_to_id must hold 1..{F.LANG_MAX} distinct ids in [0, {V}); got "
-                         f"{len(ids)} ids from {ids[0]} to {ids[-1]}")
-    return ids
-
-
-def language_rows(gc, language, B):
-    """generate's `language` -> None (no language token), AUTO, or one language id per row.  A list or tuple names
-    one language per row, each whatever a single `language` may be; HF's errors (_retrieve_init_tokens): TypeError
-    for a None element, ValueError for a length other than the batch size."""
-    if isinstance(language, (list, tuple)):
-        if any(l is None for l in language):
-            raise TypeError("Expected `language` to be `None`, a single string (e.g. `'en'`), or a list of strings "
-                            "with length equal to the batch size (e.g. `('en', 'fr')` for a batch size of 2). Got a "
-                            "list containing `None`.")
-        if len(language) != B:
-            raise ValueError("When passing a list of languages, the length of the list must match the batch size. "
-                             f"Expected length of {B}, but got {len(language)} languages.")
-        return [_lang_id(gc, l) for l in language]
-    if isinstance(language, str) and language == AUTO:
-        return AUTO
-    lid = _lang_id(gc, language)
-    return None if lid is None else [lid] * B
-
-
 def _detect(model, gc, enc16, B, Tk, want_probs=False):
     """HF detect_language's decoder part on B clips' encoder rows: one step at position 0 on <|startoftranscript|>
     through a DecodeSession, then tw_lang_detect over the language ids -> (ids int64 [B], probs fp32 [B, L] or None,
@@ -393,6 +330,26 @@ def _resolve_gc(model):
     return gc
 
 
+def _unwrap(encoder_outputs):
+    """The encoder's last hidden state [B, Tk, d] out of what a caller passes as encoder_outputs (HF's ModelOutput or
+    a tuple); None stays None."""
+    if encoder_outputs is None:
+        return None
+    return encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
+
+
+def _encoder_rows(model, features, hidden):
+    """The encoder rows a decode reads -> (enc16 [B * Tk, d] on the device, B, Tk): the caller's own encoder output
+    `hidden` (_unwrap) when there is one, else `features` through the model's encoder."""
+    if hidden is not None:
+        B, Tk = hidden.shape[0], hidden.shape[1]
+        return hidden.reshape(-1, model.config.d_model).to(model.device, model.act_dtype).contiguous(), B, Tk
+    conv_in = model.conv_input(features)
+    enc16 = model.encode(conv_in)
+    B = conv_in.shape[0]
+    return enc16, B, enc16.shape[0] // B
+
+
 @torch.no_grad()
 def detect_language(model, input_features=None, encoder_outputs=None, return_probs=False):
     """HF WhisperGenerationMixin.detect_language (transformers 5.15 generation_whisper.py:1610-1673): the language
@@ -409,16 +366,8 @@ def detect_language(model, input_features=None, encoder_outputs=None, return_pro
         raise ValueError("Make sure to specify only one of `input_features` or `encoder_outputs` - not both!")
     gc = _resolve_gc(model)
     language_table(gc, model.config.vocab_size)
-    cfg = model.config
-    if encoder_outputs is not None:
-        enc = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
-        B, Tk = enc.shape[0], enc.shape[1]
-        enc16 = enc.reshape(-1, cfg.d_model).to(model.device, model.act_dtype).contiguous()
-    else:
-        conv_in = model.conv_input(_first_window(model, input_features))
-        enc16 = model.encode(conv_in)
-        B = conv_in.shape[0]
-        Tk = enc16.shape[0] // B
+    feats = _first_window(model, input_features) if input_features is not None else None
+    enc16, B, Tk = _encoder_rows(model, feats, _unwrap(encoder_outputs))
     ids, probs, table = _detect(model, gc, enc16, B, Tk, return_probs)
     return (ids, probs, table) if return_probs else ids
 
@@ -587,15 +536,6 @@ class _Decoder(_PromptedDecode):
             if (t - P) % 8 == 7 and bool(sel.done.all()):
                 break
         return self._trim(t)
-
-
-# Drafted tokens per round when generate(assistant_model=...) is given no num_assistant_tokens.  A guess from byte
-# counts, not a measurement: a large-v2 verify pass reads the decoder's weights once whatever Q is, a distil-32-2
-# draft step reads 1/16 of the layers plus the LM head, so a handful of drafts costs little beside one target step
-# (tools/bench_spec.py times both; the end-to-end gain depends on the acceptance rate of real checkpoints, which is
-# unmeasured).  HF's default (20 with a heuristic schedule) differs; for greedy decoding the output does not depend on it.
-DEFAULT_ASSISTANT_TOKENS = 4
-MAX_ASSISTANT_TOKENS = F.MQ_MAX - 1
 
 
 class _SpecDecoder(_PromptedDecode):
@@ -899,19 +839,6 @@ class _BeamDecoder:
         return best[:, P:P + gen_len]
 
 
-def total_length(cfg, gc, P, max_length=None, max_new_tokens=None):
-    """Length cap of prompt + generated tokens, HF _set_max_new_tokens_and_length
-    (generation_whisper.py:1919-1945): max_new_tokens counts after the P prompt tokens; a max_length
-    (the call's, else generation_config's) is raised by the min(max_target_positions // 2 - 1, P)
-    initial tokens; both capped at max_target_positions."""
-    if max_new_tokens is not None:
-        total = P + int(max_new_tokens)
-    else:
-        ml = max_length or gc.max_length or cfg.max_target_positions
-        total = int(ml) + min(cfg.max_target_positions // 2 - 1, P)
-    return min(total, cfg.max_target_positions)
-
-
 def retrieve_segment(seq, seek_num_frames, ts_begin=50364, input_stride=2):
     """HF `_retrieve_segment` (generation_whisper.py), token part: split a window's tokens at
     consecutive timestamp pairs -> (segments, seek offset in feature frames)."""
@@ -933,35 +860,23 @@ def retrieve_segment(seq, seek_num_frames, ts_begin=50364, input_stride=2):
     return segs, off
 
 
-# keywords generate implements beyond its named parameters (the fallback settings of HF's long-form generate, the
-# engine's own switches and the tests' private hooks); anything else raises TypeError instead of being dropped
-GENERATE_KEYWORDS = frozenset({"temperature", "compression_ratio_threshold", "logprob_threshold", "no_speech_threshold",
-                               "condition_on_prev_tokens", "do_sample", "seed", "fallback_batch", "_trace", "_keep",
-                               "repetition_penalty", "no_repeat_ngram_size"})
-
-
-def repeat_options(gc, kw):
-    """generate's repetition_penalty / no_repeat_ngram_size -> (penalty, n): the call's value, else the generation
-    config's when it names one (as HF merges them), else off (1.0, 0).  HF's checks: the penalty a strictly positive
-    float (RepetitionPenaltyLogitsProcessor; 1 adds no processor, so an int 1 passes), the size a non-negative int."""
-    def pick(name):
-        v = kw.get(name)
-        return v if v is not None else (gc.get(name) if gc is not None and hasattr(gc, "get") else None)
-    p, n = pick("repetition_penalty"), pick("no_repeat_ngram_size")
-    if p is None or (not isinstance(p, bool) and isinstance(p, (int, float)) and p == 1):
-        p = 1.0
-    elif not isinstance(p, float) or not p > 0:
-        raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p!r}")
-    if n is None:
-        n = 0
-    elif isinstance(n, bool) or not isinstance(n, int) or n < 0:
-        raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {n!r}")
-    return float(p), int(n)
-
-
-def _repeat_names(penalty, ngram):
-    return " and ".join(nm for nm, on in (("repetition_penalty", penalty != 1.0), ("no_repeat_ngram_size", ngram > 0))
-                        if on)
+def _language_ids(model, gc, rq, chunks):
+    """The request's languages as one id per row, or None (no language token): the named ids as they are; "auto" with
+    a pass of its own (OWN_PASS) runs _detect on every (enc16, B, Tk) of `chunks` -- short-form: the call's encoder
+    rows; long-form: each recording's raw first window -- and reads the ids back, one readback a chunk.  Beam search
+    decodes one prompt, so rows detected as different languages raise NotImplementedError."""
+    if rq.languages != AUTO:
+        return rq.languages
+    assert rq.detection == OWN_PASS
+    langs = []
+    for enc16, B, Tk in chunks:
+        langs += _detect(model, gc, enc16, B, Tk)[0].tolist()
+        del enc16
+    if rq.num_beams > 1 and len(set(langs)) > 1:
+        what = "recordings of this call have" if rq.long_form else "rows of this call were detected as"
+        raise NotImplementedError(f"tw generate: beam search decodes one prompt for every clip; the {what} different "
+                                  f"languages ({langs})")
+    return langs
 
 
 @torch.no_grad()
@@ -1000,191 +915,72 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     return_language=True returns (ids, language ids int64 [B] on the device) for any language form but None (there is
     no language to return: ValueError).  With decoder_input_ids the caller owns the prompt: `language` is not looked
     at, as before, and return_language raises ValueError."""
-    unknown = sorted(set(kw) - GENERATE_KEYWORDS)
-    if unknown:
-        raise TypeError(f"tw generate: unsupported keyword argument(s) {', '.join(unknown)}")
-    if prompt_condition_type not in (None, "first-segment", "all-segments"):
-        raise ValueError(f"prompt_condition_type={prompt_condition_type!r}: 'first-segment' or 'all-segments'")
-    if prompt_condition_type == "all-segments":
-        raise NotImplementedError("tw generate: prompt_condition_type='all-segments' is not implemented (the prompt "
-                                  "conditions as 'first-segment', HF's default)")
-    if prompt_ids is not None:
-        prompt_ids = [int(t) for t in torch.as_tensor(prompt_ids).reshape(-1).tolist()]
-        if decoder_input_ids is not None:
-            raise ValueError("tw generate: pass prompt_ids or decoder_input_ids, not both")
-        if kw.get("condition_on_prev_tokens"):
-            raise NotImplementedError("tw generate: prompt_ids together with condition_on_prev_tokens is not "
-                                      "implemented")
-        if not prompt_ids:
-            prompt_ids = None
-    nb = 1 if num_beams is None else int(num_beams)
-    assist = check_assistant(model, assistant_model, num_assistant_tokens, nb)
-    if assist is not None:
-        rows = input_features.shape[0] if input_features is not None and encoder_outputs is None else None
-        if rows is not None and rows != 1:
-            raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
-    temperature = kw.get("temperature")
-    fb = dict(temperature=temperature if temperature is not None else 0.0,
-              compression_ratio_threshold=kw.get("compression_ratio_threshold"),
-              logprob_threshold=kw.get("logprob_threshold"), no_speech_threshold=kw.get("no_speech_threshold"),
-              condition_on_prev_tokens=bool(kw.get("condition_on_prev_tokens") or False), seed=int(kw.get("seed", 0)))
     gc = _resolve_gc(model)
-    cfg = model.config
-    penalty, ngram = repeat_options(gc, kw)
-    if penalty != 1.0 or ngram > 0:
-        # HF's beam search applies the two processors to log-probabilities, and the verify pass of assisted decoding
-        # would need a history per query row: neither is built
-        if nb > 1:
-            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with beam search (num_beams > 1) "
-                                      "is not implemented")
-        if assist is not None:
-            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with assisted decoding "
-                                      "(assistant_model) is not implemented")
-    if encoder_outputs is not None:
-        e0 = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
-        rows_in = e0.shape[0]
-    else:
-        rows_in = input_features.shape[0] if input_features is not None else 0
-    # the new forms ("auto", one language per row) are resolved here, so that their errors come before any device
-    # work; a single language is resolved where the prompt is built, as before (with decoder_input_ids it is not
-    # looked at)
-    per_row = isinstance(language, (list, tuple)) or (isinstance(language, str) and language == AUTO)
-    langs = language_rows(gc, language, rows_in) if per_row else None
-    if langs == AUTO:
-        if decoder_input_ids is not None:
-            raise ValueError("tw generate: language='auto' builds the prompt around the detected language; with "
-                             "decoder_input_ids the caller owns the prompt")
-        language_table(gc, cfg.vocab_size)
-    if return_language and language is None:
-        raise ValueError("tw generate: return_language=True needs a language (a name, a list, or 'auto')")
-    if return_language and decoder_input_ids is not None:
-        raise ValueError("tw generate: return_language=True with decoder_input_ids: the caller owns the prompt, and "
-                         "`language` is not looked at")
-    if nb > 1 and langs not in (None, AUTO) and len(set(langs)) > 1:
-        raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the rows of this call "
-                                  "name different languages")
-    use_graph = True if use_graph is None else use_graph
-    window = 2 * cfg.max_source_positions                     # 3000 feature frames = 30 s
-    # HF (generation_whisper.py:785-898) runs the seek loop for every input when timestamps are predicted, a
-    # <= 30 s one included: a window that ends on a timestamp pair before the end of the audio is followed by
-    # another window from that timestamp (tests/test_lv2_decode_gpu.py pins it at large-v2 dims)
-    seek_loop = bool(return_timestamps) and decoder_input_ids is None
-    if encoder_outputs is None and input_features is not None and (input_features.shape[-1] > window or seek_loop):
-        return _longform(model, gc, input_features, attention_mask, language, task, max_length, max_new_tokens,
-                         use_graph, window, kw.get("_trace"), fallback_batch=bool(kw.get("fallback_batch", True)),
-                         num_beams=nb, prompt_ids=prompt_ids, assist=assist, repetition_penalty=penalty,
-                         no_repeat_ngram_size=ngram, return_language=bool(return_language), **fb)
-    if kw.get("do_sample") or fb["temperature"] not in (0, 0.0) or fb["logprob_threshold"] is not None \
-            or fb["compression_ratio_threshold"] is not None or fb["no_speech_threshold"] is not None:
-        # the reference applies fallback / thresholds to long-form inputs only (run_eval.py:659-685)
-        raise NotImplementedError("tw generate: temperature fallback and thresholds apply to long-form (> 30 s) "
-                                  "inputs, as in the reference; short-form decoding is greedy")
-    if encoder_outputs is not None:
-        enc = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else encoder_outputs[0]
-        B, Tk = enc.shape[0], enc.shape[1]
-        enc16 = enc.reshape(-1, cfg.d_model).to(model.device, model.act_dtype).contiguous()
-    else:
-        conv_in = model.conv_input(input_features)
-        enc16 = model.encode(conv_in)
-        B = conv_in.shape[0]
-        Tk = enc16.shape[0] // B
+    hidden = _unwrap(encoder_outputs)
+    given = hidden if hidden is not None else input_features
+    rq = plan_generate(model.config, gc, rows=given.shape[0] if given is not None else 0,
+                       frames=input_features.shape[-1] if input_features is not None else None,
+                       have_features=input_features is not None, have_encoder_outputs=encoder_outputs is not None,
+                       max_length=max_length, num_beams=num_beams, return_timestamps=return_timestamps,
+                       language=language, task=task, decoder_input_ids=decoder_input_ids, max_new_tokens=max_new_tokens,
+                       use_graph=use_graph, prompt_ids=prompt_ids, prompt_condition_type=prompt_condition_type,
+                       assistant_model=assistant_model, num_assistant_tokens=num_assistant_tokens,
+                       return_language=return_language, **kw)
+    if rq.long_form:
+        return _longform(model, gc, rq, input_features, attention_mask)
+    cfg, dev = model.config, model.device
+    enc16, B, Tk = _encoder_rows(model, input_features, hidden)
+    # detection fused into the decode (PREFILL): the prefill's step at column 0 is the detection step, so column 1 of
+    # the prompt holds a placeholder language until the device writes the detected one there; the decoder is handed
+    # the id table and its id matrix is read afterwards
+    fused = rq.detection == PREFILL
     detect = lang_out = None
-    if decoder_input_ids is not None:
-        prompt = torch.as_tensor(decoder_input_ids, dtype=torch.int64)
+    if rq.decoder_input_ids is not None:
+        prompt = torch.as_tensor(rq.decoder_input_ids, dtype=torch.int64)
         if prompt.dim() == 1:
             prompt = prompt[None].repeat(B, 1)
-    elif langs is None:                      # one language (or none) for every row: the prompt of before
-        prompt = torch.tensor((prompt_ids or []) + build_prompt(gc, language, task, return_timestamps),
-                              dtype=torch.int64)[None].repeat(B, 1)
-        if return_language:
-            lang_out = torch.full((B,), _lang_id(gc, language), dtype=torch.int64, device=model.device)
     else:
-        auto = langs == AUTO
-        if auto and nb == 1 and assist is None and not prompt_ids:
-            # the prefill's step at column 0 is the detection step: column 1 holds a placeholder until then
+        if fused:
             table = language_table(gc, cfg.vocab_size)
-            detect = torch.tensor(table, dtype=torch.int32, device=model.device)
+            detect = torch.tensor(table, dtype=torch.int32, device=dev)
             langs = [table[0]] * B
-        elif auto:
-            # <|startoftranscript|> is not at position 0 (prompt_ids), or the decoder takes host prompts: a pass of
-            # its own over the same encoder rows, one readback of B ids
-            langs = _detect(model, gc, enc16, B, Tk)[0].tolist()
-            if nb > 1 and len(set(langs)) > 1:
-                raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the rows of "
-                                          f"this call were detected as different languages ({langs})")
-        prompt = torch.tensor([(prompt_ids or []) + build_prompt(gc, lid, task, return_timestamps, detected=auto)
-                               for lid in langs], dtype=torch.int64)
-        lang_out = torch.tensor(langs, dtype=torch.int64, device=model.device)
-
-    def result(out, dec=None):
-        if not return_language:
-            return out
-        return out, (dec.sel.ids[:, 1].clone() if detect is not None else lang_out)
+        else:
+            langs = _language_ids(model, gc, rq, [(enc16, B, Tk)])
+        prompt = torch.tensor([list(rq.prompt_ids or ()) + build_prompt(gc, lid, rq.task, rq.timestamps,
+                                                                         detected=rq.detected)
+                               for lid in (langs if langs is not None else [None] * B)], dtype=torch.int64)
+        if rq.return_language and not fused:
+            lang_out = torch.tensor(langs, dtype=torch.int64, device=dev)
     P = prompt.shape[1]
-    max_length = total_length(cfg, gc, P, max_length, max_new_tokens)
-    if P >= max_length:
-        if return_language and detect is not None:
-            lang_out, detect = _detect(model, gc, enc16, B, Tk)[0], None
-        return result(torch.empty(B, 0, dtype=torch.int64, device=model.device))
-    if assist is not None:
+    ml = total_length(cfg, gc, P, rq.max_length, rq.max_new_tokens)
+    if P >= ml:
+        # nothing is decoded, so there is no prefill to detect in: the languages, when asked for, take their own pass
+        if fused and rq.return_language:
+            lang_out = _detect(model, gc, enc16, B, Tk)[0]
+        out = torch.empty(B, 0, dtype=torch.int64, device=dev)
+    elif rq.decoder == ASSISTED:
         if B != 1:
             raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
-        enc_a = assistant_encoder(assist[0], model, enc16, input_features)
-        dec = _SpecDecoder(model, assist[0], gc, Tk, P, max_length, bool(return_timestamps), use_graph, k=assist[1])
-        if kw.get("_keep") is not None:
-            kw["_keep"].append(dec)
-        out = dec.run(enc16, prompt.to(model.device), enc_a=enc_a)
-        if kw.get("_trace") is not None:
-            kw["_trace"].append(dict(accepted=list(dec.accepted), num_assistant_tokens=dec.k))
-        return result(out)
-    if nb > 1:
+        enc_a = assistant_encoder(rq.assistant, model, enc16, input_features)
+        dec = _SpecDecoder(model, rq.assistant, gc, Tk, P, ml, rq.timestamps, rq.use_graph, k=rq.k)
+        if rq.keep is not None:
+            rq.keep.append(dec)
+        out = dec.run(enc16, prompt.to(dev), enc_a=enc_a)
+        if rq.trace is not None:
+            rq.trace.append(dict(accepted=list(dec.accepted), num_assistant_tokens=dec.k))
+    elif rq.decoder == BEAM:
         if not bool((prompt == prompt[:1]).all()):
             raise NotImplementedError("tw generate: beam search takes one prompt for every clip")
-        return result(_BeamDecoder(model, gc, B, nb, Tk, P, max_length).run(enc16, prompt[0]))
-    dec = _Decoder(model, gc, B, Tk, P, max_length, bool(return_timestamps), use_graph, repetition_penalty=penalty,
-                   no_repeat_ngram_size=ngram)
-    if kw.get("_keep") is not None:          # tests: the decoder (and its device caches) outlive the call
-        kw["_keep"].append(dec)
-    if detect is None:
-        return result(dec.run(enc16, prompt.to(model.device)))
-    return result(dec.run(enc16, prompt.to(model.device), detect=detect), dec)
-
-
-_ASSIST_GC_KEYS = ("eos_token_id", "pad_token_id", "decoder_start_token_id", "suppress_tokens", "begin_suppress_tokens",
-                   "no_timestamps_token_id", "max_initial_timestamp_index", "lang_to_id", "task_to_id")
-
-
-def check_assistant(model, assistant, num_assistant_tokens, num_beams):
-    """The argument checks of generate(assistant_model=...) -> None or (assistant, k).  ValueError: beam search with
-    an assistant (as HF), a vocabulary or generation config that differs from the target's (the drafts are compared
-    id by id and selected with the target's rules), a decoder-only assistant of another width."""
-    if assistant is None:
-        if num_assistant_tokens is not None:
-            raise ValueError("tw generate: num_assistant_tokens needs an assistant_model")
-        return None
-    if num_beams > 1:
-        raise ValueError("tw generate: assisted decoding is greedy (num_beams must be 1), as HF's is")
-    k = DEFAULT_ASSISTANT_TOKENS if num_assistant_tokens is None else int(num_assistant_tokens)
-    if k < 1:
-        raise ValueError(f"num_assistant_tokens={num_assistant_tokens!r}: at least 1")
-    k = min(k, MAX_ASSISTANT_TOKENS)
-    cfg, ac = model.config, getattr(assistant, "config", None)
-    if ac is None:
-        raise ValueError("tw generate: assistant_model must be a tw WhisperForConditionalGeneration or WhisperForCausalLM")
-    if ac.vocab_size != cfg.vocab_size:
-        raise ValueError(f"tw generate: the assistant's vocabulary ({ac.vocab_size}) differs from the target's "
-                         f"({cfg.vocab_size})")
-    ga, gt = assistant.generation_config, model.generation_config
-    if ga is not None and gt is not None:
-        for key in _ASSIST_GC_KEYS:
-            va, vt = (ga.get(key) if hasattr(ga, "get") else getattr(ga, key, None)), \
-                (gt.get(key) if hasattr(gt, "get") else getattr(gt, key, None))
-            if va is not None and vt is not None and va != vt:
-                raise ValueError(f"tw generate: the assistant's generation config differs from the target's in {key}")
-    if getattr(assistant, "decoder_only", False) and ac.d_model != cfg.d_model:
-        raise ValueError(f"tw generate: a decoder-only assistant decodes over the target's encoder output: d_model "
-                         f"{ac.d_model} != {cfg.d_model}")
-    return assistant, k
+        out = _BeamDecoder(model, gc, B, rq.num_beams, Tk, P, ml).run(enc16, prompt[0])
+    else:
+        dec = _Decoder(model, gc, B, Tk, P, ml, rq.timestamps, rq.use_graph, repetition_penalty=rq.repetition_penalty,
+                       no_repeat_ngram_size=rq.no_repeat_ngram_size)
+        if rq.keep is not None:              # tests: the decoder (and its device caches) outlive the call
+            rq.keep.append(dec)
+        out = dec.run(enc16, prompt.to(dev), **(dict(detect=detect) if fused else {}))
+        if fused and rq.return_language:
+            lang_out = dec.sel.ids[:, 1].clone()
+    return (out, lang_out) if rq.return_language else out
 
 
 def assistant_encoder(assistant, model, enc16, input_features):
@@ -1310,18 +1106,12 @@ class _LongForm:
     conditioned form starts once the group's first recording has a segment, and from then on a row without previous
     text carries <|startofprev|> alone (no <|startofprev|> id: the rows condition without it).
     init: per recording of the call, prompt_ids + task prompt, the unconditioned prompt (the recordings' language
-    tokens may differ, the lengths do not); n_task: the length of its task part.  assist =
-    (assistant, k), one recording: the temperature-0 attempt of each window is assisted (_SpecDecoder)."""
+    tokens may differ, the lengths do not); n_task: the length of its task part.  An assisted request (one recording):
+    the temperature-0 attempt of each window is assisted (_SpecDecoder).  The fields are the request and what is
+    derived from it once per call; the request's own settings are read from rq."""
     model: object
     gc: object
-    temps: tuple
-    track: bool
-    window: int
-    compression_ratio_threshold: float
-    logprob_threshold: float
-    no_speech_threshold: float
-    fallback_batch: bool
-    cond: bool
+    rq: Request
     eos: int
     pad: int
     ts_begin: int
@@ -1330,21 +1120,12 @@ class _LongForm:
     cut_off: int
     init: list
     n_task: int
-    max_length: int
-    max_new_tokens: int
-    use_graph: bool
-    assist: tuple
-    repetition_penalty: float
-    no_repeat_ngram_size: int
-    num_beams: int
-    seed: int
-    trace: list
     enc_rows: int = 32              # windows per encoder call (bounds the encoder's activations)
     decoders: dict = dataclasses.field(default_factory=dict)
 
     def decoder(self, P, ml, nb=1, spec=False):
         # the two repeat options are baked into a captured step
-        key = (P, ml, nb, spec, self.repetition_penalty, self.no_repeat_ngram_size)
+        key = (P, ml, nb, spec, self.rq.repetition_penalty, self.rq.no_repeat_ngram_size)
         if key in self.decoders:
             self.decoders[key] = self.decoders.pop(key)      # most recently used last
         else:
@@ -1354,17 +1135,18 @@ class _LongForm:
                 self.decoders.pop(next(iter(self.decoders)))
             m, Tk = self.model, self.model.config.max_source_positions
             if spec:
-                self.decoders[key] = _SpecDecoder(m, self.assist[0], self.gc, Tk, P, ml, True, self.use_graph,
-                                                  self.track, k=self.assist[1])
+                self.decoders[key] = _SpecDecoder(m, self.rq.assistant, self.gc, Tk, P, ml, True, self.rq.use_graph,
+                                                  self.rq.track, k=self.rq.k)
             else:
-                self.decoders[key] = _Decoder(m, self.gc, nb, Tk, P, ml, True, self.use_graph, self.track,
-                                              repetition_penalty=self.repetition_penalty,
-                                              no_repeat_ngram_size=self.no_repeat_ngram_size)
+                self.decoders[key] = _Decoder(m, self.gc, nb, Tk, P, ml, True, self.rq.use_graph, self.rq.track,
+                                              repetition_penalty=self.rq.repetition_penalty,
+                                              no_repeat_ngram_size=self.rq.no_repeat_ngram_size)
         return self.decoders[key]
 
     def seeds(self, b, nwin):
         """One seed per temperature level for window nwin of recording b (its index in the call)."""
-        return [(self.seed * 1000003 + b * 7919 + nwin * 131 + fi) & ((1 << 63) - 1) for fi in range(len(self.temps))]
+        return [(self.rq.seed * 1000003 + b * 7919 + nwin * 131 + fi) & ((1 << 63) - 1)
+                for fi in range(len(self.rq.temps))]
 
     # One attempt of the fallback ladder on the window state w (enc, enc_a, prompts, P, ml, ns, seeds, padded) ->
     # (raw tokens per attempt, gate(r, n) -> (avg_logprob over n tokens, no_speech_prob) of row r, read back only when
@@ -1378,9 +1160,9 @@ class _LongForm:
         rows = attempts + [attempts[0]] * (nb - len(attempts))
         b0 = rows[0][0]
         e16 = w.enc[b0] if len({b for b, _ in rows}) == 1 else torch.cat([w.enc[b] for b, _ in rows])
-        tl = [self.temps[f] or 0.0 for _, f in rows]
+        tl = [self.rq.temps[f] or 0.0 for _, f in rows]
         sl = [w.seeds[b][f] for b, f in rows]
-        assisted = self.assist is not None and nb == 1 and not tl[0]
+        assisted = self.rq.decoder == ASSISTED and nb == 1 and not tl[0]
         dec = self.decoder(w.P, w.ml, nb, spec=assisted)
         pads = [w.P - len(w.prompts[b]) for b, _ in rows]
         prompt = torch.tensor([[self.pad] * n + w.prompts[b] for n, (b, _) in zip(pads, rows)], dtype=torch.int64,
@@ -1394,7 +1176,7 @@ class _LongForm:
         raws = [row_tokens(r, self.eos) for r in dec.run(e16, prompt, **kw).tolist()[:len(attempts)]]
 
         def gate(r, n):
-            return (float(dec.sel.sum_logp[r]) / n if self.track else 0.0,
+            return (float(dec.sel.sum_logp[r]) / n if self.rq.track else 0.0,
                     float(torch.exp(dec.ns_logp[r])) if w.ns is not None else 0.0)
         return raws, gate, nb, list(dec.accepted) if assisted else None
 
@@ -1405,7 +1187,7 @@ class _LongForm:
         gc = self.gc
         beam_ts = (self.ts_begin, int(gc.no_timestamps_token_id),
                    gc.max_initial_timestamp_index if "max_initial_timestamp_index" in gc else None)
-        bd = _BeamDecoder(self.model, gc, 1, self.num_beams, self.model.config.max_source_positions, w.P, w.ml,
+        bd = _BeamDecoder(self.model, gc, 1, self.rq.num_beams, self.model.config.max_source_positions, w.P, w.ml,
                           timestamps=beam_ts)
         raw = row_tokens(bd.run(w.enc[b], w.prompts[b], no_speech=w.ns)[0].tolist(), self.eos)
 
@@ -1415,17 +1197,19 @@ class _LongForm:
 
     def run(self, feats, lens, recs):
         """The seek loop over the recordings `recs` (their indices in the call) -> {recording: its tokens}."""
-        model, temps, window, eos, pad, trace = self.model, self.temps, self.window, self.eos, self.pad, self.trace
+        model, rq, eos, pad = self.model, self.rq, self.eos, self.pad
+        temps, trace, cond = rq.temps, rq.trace, rq.condition_on_prev_tokens
+        window = 2 * model.config.max_source_positions            # 3000 feature frames = 30 s
         dev, nmel, V = model.device, feats.shape[1], model.config.vocab_size
-        spec = self.fallback_batch and batch_rows_independent(model)
+        spec = rq.fallback_batch and batch_rows_independent(model)
         # a beam search at temperature 0 later in the schedule decodes alone: the levels are taken one at a time
-        one_level = self.num_beams > 1 and any(not t for t in temps[1:])
-        assert self.num_beams == 1 or len(recs) == 1
+        one_level = rq.num_beams > 1 and any(not t for t in temps[1:])
+        assert rq.num_beams == 1 or len(recs) == 1
         seek = {b: 0 for b in recs}
         nwin = {b: 0 for b in recs}
         outs = {b: [] for b in recs}
         segments = {b: [] for b in recs}         # accepted segments per recording (the previous text)
-        cond_on = {b: self.cond for b in recs}
+        cond_on = {b: cond for b in recs}
         while True:
             active = [b for b in recs if seek[b] < int(lens[b])]          # _maybe_reduce_batch
             if not active:
@@ -1434,13 +1218,13 @@ class _LongForm:
             prompts, P = conditioned_prompts(None, [segments[b] for b in active], [cond_on[b] for b in active],
                                              any(cond_on.values()) and len(segments[recs[0]]) > 0, self.prev_sot,
                                              self.cut_off, self.ts_begin, inits=[self.init[b] for b in active])
-            ml = total_length(model.config, self.gc, P, self.max_length, self.max_new_tokens)
+            ml = total_length(model.config, self.gc, P, rq.max_length, rq.max_new_tokens)
             if P >= ml:
                 raise ValueError(f"prompt of {P} tokens leaves no room below max_length {ml}")
             w = types.SimpleNamespace(enc={}, enc_a={}, prompts=dict(zip(active, prompts)), P=P, ml=ml,
-                                      ns=(P - self.n_task, self.ns_token) if self.no_speech_threshold is not None
+                                      ns=(P - self.n_task, self.ns_token) if rq.no_speech_threshold is not None
                                       else None, seeds={b: self.seeds(b, nwin[b]) for b in active},
-                                      padded=self.cond and len(recs) > 1)
+                                      padded=cond and len(recs) > 1)
             # encode the current windows together (chunks of enc_rows)
             for c0 in range(0, len(active), self.enc_rows):
                 rows = active[c0:c0 + self.enc_rows]
@@ -1451,8 +1235,8 @@ class _LongForm:
                 tk = e.shape[0] // len(rows)
                 for i, b in enumerate(rows):
                     w.enc[b] = e[i * tk:(i + 1) * tk]
-                if self.assist is not None:          # one recording: the assistant's rows for the same window
-                    w.enc_a[rows[0]] = assistant_encoder(self.assist[0], model, w.enc[rows[0]], segb)
+                if rq.decoder == ASSISTED:          # one recording: the assistant's rows for the same window
+                    w.enc_a[rows[0]] = assistant_encoder(rq.assistant, model, w.enc[rows[0]], segb)
                 del segb
             result = {}                       # b -> (last attempt's tokens, skip, its temperature)
             pending = list(active)
@@ -1461,7 +1245,7 @@ class _LongForm:
                 per = max(1, 8 // len(pending)) if spec and level > 0 and not one_level else 1
                 levels = list(range(level, min(len(temps), level + per)))
                 attempts = [(b, f) for f in levels for b in pending]
-                beam = self.num_beams > 1 and len(levels) == 1 and not temps[level]
+                beam = rq.num_beams > 1 and len(levels) == 1 and not temps[level]
                 raws, gate, batch, accepted = self.decode_beam(w, pending[0]) if beam else self.decode_rows(w, attempts)
                 decided = set()
                 for r, (b, f) in enumerate(attempts):
@@ -1470,12 +1254,12 @@ class _LongForm:
                     raw = raws[r]
                     needs, skip = False, False
                     rec = dict(b=b, seek=seek[b], n=nfr[b], T=temps[f], prompt=list(w.prompts[b]), raw=list(raw))
-                    if self.track or self.compression_ratio_threshold is not None or beam:
+                    if rq.track or rq.compression_ratio_threshold is not None or beam:
                         tg = time.perf_counter()      # gate cost: log-prob / no-speech readback + compression ratio
                         cand = trim_pads(raw, pad, eos)
                         avg, nsp = gate(r, max(len(cand), 1))
-                        needs, skip = need_fallback(cand, avg, nsp, V, self.compression_ratio_threshold,
-                                                    self.logprob_threshold, self.no_speech_threshold)
+                        needs, skip = need_fallback(cand, avg, nsp, V, rq.compression_ratio_threshold,
+                                                    rq.logprob_threshold, rq.no_speech_threshold)
                         rec.update(avg_logprob=avg, no_speech_prob=nsp, needs_fallback=needs, skip=skip, batch=batch,
                                    gate_ms=(time.perf_counter() - tg) * 1e3)
                     else:
@@ -1494,7 +1278,7 @@ class _LongForm:
                 seq, skip, t_acc = result[b]
                 n = nfr[b]
                 nwin[b] += 1
-                cond_on[b] = self.cond and (t_acc is None or t_acc < 0.5)
+                cond_on[b] = cond and (t_acc is None or t_acc < 0.5)
                 if not skip:
                     if seek[b] + window < int(lens[b]) and seq and seq[-1] == eos:    # not the last window: cut its eos
                         seq = seq[:-1]
@@ -1505,16 +1289,13 @@ class _LongForm:
                 segs, off = retrieve_segment(seq, n, self.ts_begin)
                 for sgm in segs:
                     outs[b].extend(sgm)
-                    if self.cond:
+                    if cond:
                         segments[b].append(list(sgm))
                 seek[b] += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
         return outs
 
 
-def _longform(model, gc, feats, attention_mask, language, task, max_length, max_new_tokens, use_graph, window,
-              trace=None, temperature=0.0, compression_ratio_threshold=None, logprob_threshold=None,
-              no_speech_threshold=None, condition_on_prev_tokens=False, seed=0, fallback_batch=True, num_beams=1,
-              prompt_ids=None, assist=None, repetition_penalty=1.0, no_repeat_ngram_size=0, return_language=False):
+def _longform(model, gc, rq, feats, attention_mask):
     """HF sequential long-form generate (generation_whisper.py step 6): per input, 30 s windows from `seek`, decoded
     with the timestamp rules and HF's temperature fallback; trailing eos/pad trimmed, segments split at consecutive
     timestamps, seek advanced by the last timestamp (or the whole window on a single-timestamp ending).  Returns the
@@ -1524,58 +1305,42 @@ def _longform(model, gc, feats, attention_mask, language, task, max_length, max_
     decode as one batch.  num_beams > 1 (run_eval.py --num_beams with timestamps / long-form): every recording is a
     group of its own, in recording order, so each window is encoded alone (the encoder's output depends on the batch
     it runs in); a temperature-0 attempt is a beam search over the window, a sampled attempt keeps one beam.
-    language: what generate takes.  A list, or "auto", gives every recording its own task prompt for all of its
-    windows; "auto" detects once per call, as HF does, on the first 3000 raw frames of every recording (HF's
+    rq: the call's Request.  Its languages give every recording its own task prompt for all of its windows; "auto"
+    detects once per call, as HF does, on the first 3000 raw frames of every recording (HF's
     input_features[:, :, :3000], not the zero-filled window the seek loop cuts), enc_rows recordings at a time.
-    return_language: -> (ids, language ids int64 [B])."""
+    rq.return_language: -> (ids, language ids int64 [B])."""
     cfg = model.config
     feats = feats.to(model.device, torch.float32)
     B, _, T = feats.shape
     lens = attention_mask.sum(-1).tolist() if attention_mask is not None else [T] * B
-    nbeam = max(1, int(num_beams or 1))
-    langs = language_rows(gc, language, B)
-    if return_language and langs is None:
-        raise ValueError("tw generate: return_language=True needs a language (a name, a list, or 'auto')")
-    auto = langs == AUTO
-    if auto:
-        language_table(gc, cfg.vocab_size)
-        langs = []
+
+    def first_windows():
         for c0 in range(0, B, _LongForm.enc_rows):
             e = model.encode(model.conv_input(_first_window(model, feats[c0:c0 + _LongForm.enc_rows])))
             n = min(B, c0 + _LongForm.enc_rows) - c0
-            langs += _detect(model, gc, e, n, e.shape[0] // n)[0].tolist()
-            del e
-    if nbeam > 1 and langs is not None and len(set(langs)) > 1:
-        raise NotImplementedError("tw generate: beam search decodes one prompt for every clip; the recordings of this "
-                                  f"call have different languages ({langs})")
-    task_inits = [build_prompt(gc, lid, task, True, detected=auto) for lid in (langs if langs is not None else [None])]
-    task_init = task_inits[0] if task_inits else build_prompt(gc, None, task, True)
-    temps = tuple(temperature) if isinstance(temperature, (list, tuple)) else (temperature,)
-    track = (logprob_threshold is not None or no_speech_threshold is not None or any(t and t > 0 for t in temps)
-             or len(temps) > 1)
+            yield e, n, e.shape[0] // n
+            del e                             # before the next chunk is encoded
+    langs = _language_ids(model, gc, rq, first_windows())
+    task_inits = [build_prompt(gc, lid, rq.task, True, detected=rq.detected)
+                  for lid in (langs if langs is not None else [None] * B)]
     eos, pad = int(gc.eos_token_id), int(gc.pad_token_id if gc.pad_token_id is not None else gc.eos_token_id)
-    prev_sot = gc.get("prev_sot_token_id") if hasattr(gc, "get") else None
+    prev_sot = gc_get(gc, "prev_sot_token_id")
     if prev_sot is None:
         sup = list(gc.suppress_tokens or [])
         prev_sot = sup[-2] if len(sup) >= 2 else None
-    lf = _LongForm(model=model, gc=gc, temps=temps, track=track, window=window,
-                   compression_ratio_threshold=compression_ratio_threshold, logprob_threshold=logprob_threshold,
-                   no_speech_threshold=no_speech_threshold, fallback_batch=fallback_batch,
-                   cond=bool(condition_on_prev_tokens), eos=eos, pad=pad, ts_begin=int(gc.no_timestamps_token_id) + 1,
+    lf = _LongForm(model=model, gc=gc, rq=rq, eos=eos, pad=pad, ts_begin=int(gc.no_timestamps_token_id) + 1,
                    ns_token=int(gc.no_timestamps_token_id) - 1, prev_sot=prev_sot,
                    cut_off=cfg.max_target_positions // 2 - 1,
                    # prompt_ids: in front of every window's task prompt
-                   init=[list(prompt_ids or []) + (task_inits[b] if langs is not None else task_init) for b in range(B)],
-                   n_task=len(task_init), max_length=max_length, max_new_tokens=max_new_tokens, use_graph=use_graph,
-                   assist=assist, repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
-                   num_beams=nbeam, seed=seed, trace=trace)
+                   init=[list(rq.prompt_ids or ()) + t for t in task_inits],
+                   n_task=len(task_inits[0]) if task_inits else 0)
     outs = {}
-    for recs in ([list(range(B))] if nbeam == 1 else [[b] for b in range(B)]):
+    for recs in ([list(range(B))] if rq.num_beams == 1 else [[b] for b in range(B)]):
         outs.update(lf.run(feats, lens, recs))
     L = max((len(o) for o in outs.values()), default=0)
     res = torch.full((B, L), pad, dtype=torch.int64)
     for b, o in outs.items():
         res[b, :len(o)] = torch.tensor(o, dtype=torch.int64)
-    if return_language:
+    if rq.return_language:
         return res.to(model.device), torch.tensor(langs, dtype=torch.int64, device=model.device)
     return res.to(model.device)

@@ -1,5 +1,5 @@
-"""The long-form host logic (tw/generation.py _longform) as a table of cases over scripted stand-ins: with the device
-decoders scripted the seek loop is pure Python, so its outputs can be compared exactly between two commits.
+"""The long-form host logic (tw/generation.py generate -> _longform) as a table of cases over scripted stand-ins: with
+the device decoders scripted the seek loop is pure Python, so its outputs can be compared exactly between two commits.
 tests/golden/make_golden_longform_host.py records the table on one commit (longform_host.json);
 tests/test_longform_host_cpu.py runs it on the working tree and compares.
 
@@ -96,7 +96,8 @@ class ScriptedBeamDecoder:
 
 def model(compute="bf16"):
     cfg = types.SimpleNamespace(max_source_positions=1500, max_target_positions=448, vocab_size=51865, d_model=128)
-    m = types.SimpleNamespace(config=cfg, device=torch.device("cpu"), compute=compute, act_dtype=torch.float32)
+    m = types.SimpleNamespace(config=cfg, device=torch.device("cpu"), compute=compute, act_dtype=torch.float32,
+                              generation_config=_gc())
     m.conv_input = lambda feats: feats
 
     def encode(x):
@@ -198,14 +199,16 @@ def run_case(generation, case):
     m = model(case.get("compute", "bf16"))
     assist = None
     if case.get("assist"):          # an assistant with an encoder of its own (its calls are recorded with the target's)
-        assist = (types.SimpleNamespace(decoder_only=False, conv_input=m.conv_input, encode=m.encode), case["assist"])
+        assist = types.SimpleNamespace(decoder_only=False, conv_input=m.conv_input, encode=m.encode, config=m.config,
+                                       generation_config=None)
     feats, mask = features(case["frames"])
     trace = []
     try:
         for n, cls in names.items():
             setattr(generation, n, cls)
-        out = generation._longform(m, _gc(), feats, mask, "zh", "transcribe", None, 40, False, 3000, trace,
-                                   assist=assist, **case["kw"])
+        out = generation.generate(m, feats, attention_mask=mask, language="zh", task="transcribe", max_new_tokens=40,
+                                  use_graph=False, return_timestamps=True, _trace=trace, assistant_model=assist,
+                                  num_assistant_tokens=case.get("assist"), **case["kw"])
     finally:
         for n, cls in saved.items():
             setattr(generation, n, cls)

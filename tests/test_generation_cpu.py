@@ -1,5 +1,5 @@
-"""Host logic of long-form decoding (tw/generation.py _longform) with a scripted stand-in for the device decoder:
-the speculative fallback batch must give what decoding the attempts one at a time gives (HF
+"""Host logic of long-form decoding (tw/generation.py generate -> _longform) with a scripted stand-in for the device
+decoder: the speculative fallback batch must give what decoding the attempts one at a time gives (HF
 generate_with_fallback decodes them one by one: generation_whisper.py:970-1090), also when the accepted row of a
 batch finishes before another row of that batch on a window that is not the last one."""
 import types
@@ -43,12 +43,17 @@ class _ScriptedDecoder:
         return torch.tensor([r + [EOS] * (L - len(r)) for r in rows], dtype=torch.int64)
 
 
-def _model():
+def _model(gc=None, compute="bf16"):
     cfg = types.SimpleNamespace(max_source_positions=1500, max_target_positions=448, vocab_size=51865, d_model=128)
-    m = types.SimpleNamespace(config=cfg, device=torch.device("cpu"), compute="bf16")
+    m = types.SimpleNamespace(config=cfg, device=torch.device("cpu"), compute=compute, generation_config=gc)
     m.conv_input = lambda feats: feats
     m.encode = lambda x: x[:, :1, :1].reshape(-1, 1).clone()    # the window id the features carry, one row a window
     return m
+
+
+def _longform(m, feats, mask, trace, **kw):
+    return generation.generate(m, feats, attention_mask=mask, language="zh", task="transcribe",
+                               max_new_tokens=40, use_graph=False, return_timestamps=True, _trace=trace, **kw)
 
 
 def _run(monkeypatch, fallback_batch, script):
@@ -59,9 +64,8 @@ def _run(monkeypatch, fallback_batch, script):
     gc = GenerationConfig(decoder_start_token_id=50258, eos_token_id=EOS, pad_token_id=EOS,
                           no_timestamps_token_id=50363, suppress_tokens=[], lang_to_id={"<|zh|>": 50260})
     trace = []
-    out = generation._longform(_model(), gc, feats, None, "zh", "transcribe", None, 40, False, 3000, trace,
-                               temperature=(0.0, 0.2, 0.4, 0.6), compression_ratio_threshold=1.35,
-                               fallback_batch=fallback_batch)
+    out = _longform(_model(gc), feats, None, trace, temperature=(0.0, 0.2, 0.4, 0.6),
+                    compression_ratio_threshold=1.35, fallback_batch=fallback_batch)
     return out[0].tolist(), trace
 
 
@@ -100,8 +104,8 @@ def test_batched_recordings_stay_together(monkeypatch):
     gc = GenerationConfig(decoder_start_token_id=50258, eos_token_id=EOS, pad_token_id=EOS,
                           no_timestamps_token_id=50363, suppress_tokens=[], lang_to_id={"<|zh|>": 50260})
     trace = []
-    out = generation._longform(_model(), gc, feats, mask, "zh", "transcribe", None, 40, False, 3000, trace,
-                               temperature=(0.0, 0.2, 0.4, 0.6), compression_ratio_threshold=1.35)
+    out = _longform(_model(gc), feats, mask, trace, temperature=(0.0, 0.2, 0.4, 0.6),
+                    compression_ratio_threshold=1.35)
     assert out[0].tolist() == [TS0, 100, 101, TS0 + 100, TS0, 400, 401, TS0 + 50, EOS]
     assert out[1].tolist()[:5] == [TS0, 500, 501, TS0 + 20, EOS] and set(out[1].tolist()[5:]) <= {EOS}
     first = [t for t in trace if t["T"] == 0.0 and t["seek"] == 0]
@@ -133,9 +137,8 @@ def test_batched_recordings_empty_and_level_by_level(monkeypatch):
     for fb in (True, False):
         _ScriptedDecoder.script = script
         trace = []
-        out = generation._longform(_model(), gc, feats, mask, "zh", "transcribe", None, 40, False, 3000, trace,
-                                   temperature=(0.0, 0.2, 0.4, 0.6), compression_ratio_threshold=1.35,
-                                   fallback_batch=fb)
+        out = _longform(_model(gc), feats, mask, trace, temperature=(0.0, 0.2, 0.4, 0.6),
+                        compression_ratio_threshold=1.35, fallback_batch=fb)
         assert 1 not in {t["b"] for t in trace}
         assert set(out[1].tolist()) == {EOS}
         if not fb:
@@ -154,14 +157,12 @@ def test_row_tokens():
 def test_fallback_batch_only_where_rows_are_independent(monkeypatch, compute, batched):
     monkeypatch.setattr(generation, "_Decoder", _ScriptedDecoder)
     _ScriptedDecoder.script = _script()
-    m = _model()
-    m.compute = compute
     feats = torch.zeros(1, 80, 6000)
     feats[..., 3000:] = 1.0
     gc = GenerationConfig(eos_token_id=EOS, pad_token_id=EOS, lang_to_id={"<|zh|>": 50260})
     trace = []
-    generation._longform(m, gc, feats, None, "zh", "transcribe", None, 40, False, 3000, trace,
-                         temperature=(0.0, 0.2, 0.4, 0.6), compression_ratio_threshold=1.35, fallback_batch=True)
+    _longform(_model(gc, compute), feats, None, trace, temperature=(0.0, 0.2, 0.4, 0.6),
+              compression_ratio_threshold=1.35, fallback_batch=True)
     assert any(t["batch"] > 1 for t in trace) == batched
 
 

@@ -116,8 +116,7 @@ def test_language_argument_errors():
     with pytest.raises(ValueError, match="owns the prompt"):
         generation.generate(m, FEATS, language="zh", decoder_input_ids=torch.tensor([SOT, ZH]), return_language=True)
     with pytest.raises(ValueError, match="return_language"):          # before anything is encoded or decoded
-        generation._longform(m, m.generation_config, torch.zeros(2, 80, 6000), None, None, None, None, 8, False,
-                             3000, return_language=True)
+        generation.generate(m, torch.zeros(2, 80, 6000), max_new_tokens=8, use_graph=False, return_language=True)
     with pytest.raises(NotImplementedError, match="different languages"):
         generation.generate(m, FEATS, language=["zh", "en"], num_beams=2)
     with pytest.raises(ValueError, match="either `input_features` or `encoder_outputs`"):
@@ -227,8 +226,9 @@ def _longform(monkeypatch, language, **kw):
     lh.LOG["runs"], lh.LOG["encodes"] = [], []
     feats, mask = lh.features(case["frames"])
     trace = []
-    out = generation._longform(lh.model(), lh._gc(), feats, mask, language, "transcribe", None, 40, False, 3000,
-                               trace, **case["kw"], **kw)
+    out = generation.generate(lh.model(), feats, attention_mask=mask, language=language, task="transcribe",
+                              max_new_tokens=40, use_graph=False, return_timestamps=True, _trace=trace, **case["kw"],
+                              **kw)
     return out, [{k: v for k, v in t.items() if k != "gate_ms"} for t in trace]
 
 
