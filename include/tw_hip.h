@@ -384,6 +384,44 @@ int tw_kv_append(const void* src, int64_t ld_src, void* cache, int64_t ld_row, i
                  const int* t_dev, tw_stream_t stream);
 int tw_step_advance(int* t_dev, int by, tw_stream_t stream);
 
+/* ---- 8-bit cross-attention K/V cache (model.cross_kv_dtype = "fp8_e4m3"; csrc/xkv_fp8.hip).  Opt-in: the
+ * cross-attention K/V is written once per 30 s window and read once per generated token, and that read bounds
+ * batched decoding; as bytes it is half as large and half as long to read.
+ * FORMAT.  Elements are OCP e4m3fn bytes (torch.float8_e4m3fn), rounded to nearest even.  Layout per decoder layer:
+ * K [B][H][Tk][64] bytes, then V, as tw_kv_head_major lays out 16-bit elements.  One fp32 scale per (clip, head)
+ * block of K and one of V: 2*B*H floats, the K scales then the V scales, block (b, h) at index b*H + h.  A scale is
+ * 2^e, e the smallest integer with absmax * 2^-e <= 448, absmax over the block's Tk x 64 16-bit values (absmax =
+ * m * 2^x, m in [0.5, 1): e = x - 9 when m <= 0.875, else x - 8), e clamped to [-100, 100]; absmax == 0 gives 1; a
+ * block holding an inf or NaN gets a NaN scale, so every output that reads it is NaN.  An element is
+ * RNE_e4m3(x * 2^-e): the product is exact and at most 448 in magnitude (absmax above 448 * 2^100, which the clamp
+ * would let past the format's range, is outside any 16-bit activation this engine produces).  Dequantisation
+ * (byte * 2^e) is exact: the value is a bf16 value, and an fp16 value wherever it is in fp16's normal range.
+ * tw_kv_head_major_fp8: tw_kv_head_major's source -> the bytes (dst, 2*B*H*Tk*64 of them) and the scales.  One
+ * workgroup per block, two passes (absmax, quantise).  dtype bf16 or fp16 (fp32: 2); a null pointer, ld not a
+ * multiple of 16 B or below 128*H, or a misaligned pointer: 1.
+ * tw_decode_attn_fp8: tw_decode_attn_ks (k_start may be NULL: every start 0) over such a cache.  k / v point at
+ * bytes and ldk, skb, hsk, ldv, svb, hsv count bytes; block (b, h) is scaled by k_scale[b*ssb + h] and
+ * v_scale[b*ssb + h] (ssb = 0 together with skb = svb = 0: one clip's blocks and scales for every row).  q and o are
+ * `dtype` (bf16 or fp16; fp32: 2).  K and V are converted to fp32 exactly and accumulated as in the 16-bit kernels;
+ * the K scale is folded into the score scale and the V scale applied once to the reduced output -- both exact, the
+ * scales being powers of two -- so the result is the fp32 arithmetic of tw_decode_attn_ks over the dequantised
+ * cache, in a different summation order only where the 16-bit call would take another kernel variant.  Only a
+ * fixed Tk: tk_dev != NULL returns 2 (the self-attention cache stays 16-bit).  A null scale pointer returns 1.  The
+ * variants and the split rule are tw_decode_attn_ks's; bytes below a row's start or at / past Tk are never loaded.
+ * tw_decode_attn_mq_fp8: tw_decode_attn_mq over such a cache, with the same additions and restrictions. */
+int tw_kv_head_major_fp8(const void* src, int64_t ld, void* dst, float* scales, int B, int Tk, int H, int dtype,
+                         tw_stream_t stream);
+int tw_decode_attn_fp8(const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
+                       const void* v, int64_t ldv, int64_t svb, int64_t hsv, const float* k_scale,
+                       const float* v_scale, int64_t ssb, void* o, int64_t sob, int B, int H, int Tk,
+                       const int* tk_dev, const int* k_start, int head_dim, float scale, int dtype,
+                       tw_stream_t stream);
+int tw_decode_attn_mq_fp8(const void* q, int64_t sqb, int64_t sqq, const void* k, int64_t ldk, int64_t skb,
+                          int64_t hsk, const void* v, int64_t ldv, int64_t svb, int64_t hsv, const float* k_scale,
+                          const float* v_scale, int64_t ssb, void* o, int64_t sob, int64_t soq, int B, int H, int Q,
+                          int Tk, const int* tk_dev, const int* k_start, int causal, int head_dim, float scale,
+                          int dtype, tw_stream_t stream);
+
 /* ---- fp32 arithmetic path (mixed_precision = "no", run_distillation.py:815-823: the reference's default
  * --dtype float32; the fp32 greedy decode pinned token-for-token to HF fp32 generate).  Exact-fp32 MFMA
  * (v_mfma_f32_16x16x4_f32), nothing rounded to bf16.

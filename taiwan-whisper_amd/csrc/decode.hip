@@ -30,29 +30,6 @@ namespace {
 
 using namespace twd;
 
-// effective key count of a call: the fixed Tk plus the device-side step index, bounded by the score buffer
-__device__ __forceinline__ int eff_tk(const DecP& p) { return min(p.Tk + (p.tk_dev ? *p.tk_dev : 0), DA_MAX_TK); }
-
-// per-row key start (left-padded decoder prompts: HF's decoder attention mask): row b attends keys
-// [k_start[b], tk), the start clamped into [0, tk - 1] so at least the last key -- the step's own -- is used and no
-// row below 0 or at / past tk is read.  The body walks from lo, so row b's result is bit-identical to the plain
-// call run on that row alone with K / V advanced by k_start[b] rows over tk - k_start[b] keys; without k_start
-// every row starts at key 0.  The single-query kernels take the choice as a template argument (KS): with a
-// run-time test of p.k_start the plain one-workgroup kernel measured 174 -> 186 us at 128 clips x 20 heads
-// (profiles/decode_refactor_ab.txt), so the KS = false instantiations are the kernels without the feature.
-__device__ __forceinline__ int clamp_start(const int* k_start, int b, int tk) {
-  return max(min(k_start[b], tk - 1), 0);
-}
-
-// the partial of a chunk that holds none of a query's keys (m = -inf, l = 0): the combine kernels skip it
-__device__ __forceinline__ void store_empty_partial(float* part) {
-  if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
-  if (threadIdx.x == 0) {
-    part[64] = -INFINITY;
-    part[65] = 0.f;
-  }
-}
-
 // U = loads in flight per lane, K/V streamed with nontemporal loads (round 4, tools/bench_decode_attn.py, same box,
 // profiles/r04_uv_decode_attn_ab.log): at the c4 shape (fp16, 512 clips x 20 heads over 1500 frames) U = 4 plain
 // 665 us, U = 4 nontemporal 620, U = 2 nontemporal 609 (6.45 TB/s), U = 8 782 (occupancy); at 128 x 20 pairs
@@ -99,25 +76,7 @@ __global__ __launch_bounds__(64) void decode_attn_combine_kernel(DecP p, int nch
 // unless the start reaches a query's limit -- go through decode_attn_body_mq together (each K / V row loaded once);
 // a query whose clamped start differs walks the keys from its own start, as its single-query call does, in a
 // pass of its own.
-struct MqP {
-  int64_t sqq, soq;
-  int nq, causal;
-};
-template <int QN>
-__device__ __forceinline__ void mq_group(unsigned& pend, const int (&lo)[QN], const int (&hi)[QN], int& glo,
-                                         int (&ghi)[QN]) {
-  bool found = false;
-  glo = 0;
-#pragma unroll
-  for (int j = 0; j < QN; ++j)
-    if (!found && ((pend >> j) & 1u)) { glo = lo[j]; found = true; }
-#pragma unroll
-  for (int j = 0; j < QN; ++j) {
-    const bool in = ((pend >> j) & 1u) && lo[j] == glo;
-    ghi[j] = in ? hi[j] : glo;
-    if (in) pend &= ~(1u << j);
-  }
-}
+// (MqP and mq_group: decode_impl.h)
 template <typename E, int QN>
 __global__ __launch_bounds__(DA_THREADS) void decode_attn_mq_kernel(DecP p, MqP q) {
   __shared__ float sc[DA_MQ_LDS];
@@ -800,27 +759,7 @@ SelP sel_fill(const void* logits, int64_t ld, int V, const uint32_t* suppress_bi
   return p;
 }
 
-// The checks the decode-attention entry points share (statuses as include/tw_hip.h lists them) and the DecP of the
-// call.  tk_last: the most keys a query of a fixed-Tk call attends.
-int dec_fill(DecP& p, const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk, const void* v,
-             int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int H, int Tk, int tk_last,
-             const int* tk_dev, const int* k_start, float scale) {
-  if ((!tk_dev && Tk <= 0) || tk_last > DA_MAX_TK) return TW_EUNSUPPORTED;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
-  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
-  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
-  p.q = q; p.sqb = sqb;
-  p.k = k; p.ldk = ldk; p.skb = skb;
-  p.v = v; p.ldv = ldv; p.svb = svb;
-  p.o = o; p.sob = sob;
-  p.hsk = hsk; p.hsv = hsv;
-  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.k_start = k_start; p.c = scale * 1.4426950408889634f;
-  return TW_OK;
-}
-// fixed-Tk calls on few (clip, head) pairs split the keys into chunks of DA_SPLIT (decode_attn below)
-bool dec_split(const int* tk_dev, int pairs, int nchunk) {
-  return !tk_dev && pairs < 640 && nchunk >= 2 && nchunk <= DA_MAX_CHUNK;
-}
+// (dec_fill and dec_split: decode_impl.h)
 
 // launch K<E, true> when the call has a per-row key start, K<E, false> when not
 #define DEC_LAUNCH_KS(K, grid, ...)                                                                          \

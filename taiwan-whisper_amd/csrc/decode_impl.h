@@ -2,6 +2,8 @@
 #pragma once
 #include "common.h"
 
+#include <type_traits>
+
 namespace twd {
 
 constexpr int DA_THREADS = 256;
@@ -47,13 +49,34 @@ __device__ __forceinline__ void load8_kv(const f16* p, float* o) {
 template <bool NT>
 __device__ __forceinline__ void load8_kv(const float* p, float* o) { load8(p, o); }
 
+// K/V element of the 8-bit cross-attention cache (csrc/xkv_fp8.hip): one OCP e4m3fn byte.  8 elements are one 8-B
+// load; v_cvt_pk_f32_fp8 converts two bytes of a dword at a time (exact: every e4m3 value is an fp32 value).
+struct e4m3 { uint8_t b; };
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+template <bool NT>
+__device__ __forceinline__ void load8_kv(const e4m3* p, float* o) {
+  u32x2 w;
+  if constexpr (NT) w = __builtin_nontemporal_load((const u32x2*)p);
+  else w = *(const u32x2*)p;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);
+    o[4 * j] = lo[0]; o[4 * j + 1] = lo[1]; o[4 * j + 2] = hi[0]; o[4 * j + 3] = hi[1];
+  }
+}
+
 // lane = (key slot ks = lane >> 3, 8-element chunk ch = lane & 7); a wave covers 8 keys per step.
 // E = bf16 (autocast path) or float (fp32 path: exact expf, no rounding of the output).
 // The body attends keys [lo, hi).  part == nullptr: normalise and store O.  Otherwise (split over keys,
 // flash-decoding) store the chunk's unnormalised o[64], its max m (log2 domain) and sum l to part[0..65]
 // for decode_attn_combine_kernel.
-template <typename E, int DA_U = twd::DA_U, bool NT = false>
-__device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, int lo, int hi, float* part) {
+// KV = the K / V element type: E, or e4m3 (the 8-bit cross-attention cache; K / V strides then count bytes).  Its
+// callers fold the block's K scale into p.c and pass the V scale as vs: both are powers of two, so c * sK and the
+// one multiplication of the reduced o by vs are exact, and the result is the fp32 arithmetic of the dequantised cache.
+template <typename E, int DA_U = twd::DA_U, bool NT = false, typename KV = E>
+__device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, int lo, int hi, float* part,
+                                                 float vs = 1.f) {
   __shared__ float sc[DA_MAX_TK];
   __shared__ float red[DA_THREADS / 64][64];
   __shared__ float red_l[DA_THREADS / 64];
@@ -62,8 +85,8 @@ __device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, in
   const int ks = lane >> 3, ch = lane & 7;
   constexpr bool F32 = sizeof(E) == 4;
   const E* qb = (const E*)p.q + b * p.sqb + h * 64 + ch * 8;
-  const E* kb = (const E*)p.k + b * p.skb + h * p.hsk + ch * 8;
-  const E* vb = (const E*)p.v + b * p.svb + h * p.hsv + ch * 8;
+  const KV* kb = (const KV*)p.k + b * p.skb + h * p.hsk + ch * 8;
+  const KV* vb = (const KV*)p.v + b * p.svb + h * p.hsv + ch * 8;
   float qv[8];
   load8(qb, qv);
   // pass 1: scores (log2 domain) -> LDS, running max.  A wave takes 8 keys x DA_U sub-steps per iteration
@@ -136,6 +159,7 @@ __device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, in
       acc += red[w][tid];
       lt += red_l[w];
     }
+    if constexpr (!std::is_same_v<KV, E>) acc *= vs;
     if (part) {
       part[tid] = acc;
       if (tid == 0) {
@@ -157,10 +181,11 @@ __device__ __forceinline__ void decode_attn_body(const DecP& p, int b, int h, in
 // part == nullptr: normalise and store O; otherwise query j's partial goes to part + j * pstride (66 floats).
 constexpr int DA_MQ = 8;                // most query rows per (clip, head)
 constexpr int DA_MQ_LDS = 12288;        // score floats of the one-workgroup multi-query kernel (48 KB)
-template <typename E, int QN, int DA_U = twd::DA_U, bool NT = false>
+// KV, vs: as in decode_attn_body.
+template <typename E, int QN, int DA_U = twd::DA_U, bool NT = false, typename KV = E>
 __device__ __forceinline__ void decode_attn_body_mq(const DecP& p, int64_t sqq, int64_t soq, int b, int h, int lo,
                                                     const int (&hi)[QN], float* sc, int cap, float* part,
-                                                    int64_t pstride) {
+                                                    int64_t pstride, float vs = 1.f) {
   __shared__ float red[DA_THREADS / 64][QN][64];
   __shared__ float red_l[DA_THREADS / 64][QN];
   __shared__ float red_m[DA_THREADS / 64][QN];
@@ -168,8 +193,8 @@ __device__ __forceinline__ void decode_attn_body_mq(const DecP& p, int64_t sqq, 
   const int ks = lane >> 3, ch = lane & 7;
   constexpr bool F32 = sizeof(E) == 4;
   const E* qb = (const E*)p.q + b * p.sqb + h * 64 + ch * 8;
-  const E* kb = (const E*)p.k + b * p.skb + h * p.hsk + ch * 8;
-  const E* vb = (const E*)p.v + b * p.svb + h * p.hsv + ch * 8;
+  const KV* kb = (const KV*)p.k + b * p.skb + h * p.hsk + ch * 8;
+  const KV* vb = (const KV*)p.v + b * p.svb + h * p.hsv + ch * 8;
   int himax = lo;
 #pragma unroll
   for (int j = 0; j < QN; ++j) himax = max(himax, hi[j]);
@@ -280,6 +305,7 @@ __device__ __forceinline__ void decode_attn_body_mq(const DecP& p, int64_t sqq, 
         acc += red[w][j][tid];
         lt += red_l[w][j];
       }
+      if constexpr (!std::is_same_v<KV, E>) acc *= vs;
       if (part) {
         float* pj = part + j * pstride;
         pj[tid] = acc;
@@ -323,5 +349,72 @@ __device__ __forceinline__ void combine_row(const DecP& p, int bh, int nchunk, c
   ((E*)p.o)[b * p.sob + h * 64 + lane] = e_from_f32<E>(acc / lt);
 }
 
+// ---- what the kernels of decode.hip (16-bit / fp32 K and V) and xkv_fp8.hip (e4m3 K and V) share around the bodies
+
+// effective key count of a call: the fixed Tk plus the device-side step index, bounded by the score buffer
+__device__ __forceinline__ int eff_tk(const DecP& p) { return min(p.Tk + (p.tk_dev ? *p.tk_dev : 0), DA_MAX_TK); }
+
+// per-row key start (left-padded decoder prompts: HF's decoder attention mask): row b attends keys
+// [k_start[b], tk), the start clamped into [0, tk - 1] so at least the last key -- the step's own -- is used and no
+// row below 0 or at / past tk is read.  The body walks from lo, so row b's result is bit-identical to the plain
+// call run on that row alone with K / V advanced by k_start[b] rows over tk - k_start[b] keys; without k_start
+// every row starts at key 0.  The single-query kernels take the choice as a template argument (KS): with a
+// run-time test of p.k_start the plain one-workgroup kernel measured 174 -> 186 us at 128 clips x 20 heads
+// (profiles/decode_refactor_ab.txt), so the KS = false instantiations are the kernels without the feature.
+__device__ __forceinline__ int clamp_start(const int* k_start, int b, int tk) {
+  return max(min(k_start[b], tk - 1), 0);
+}
+
+// the partial of a chunk that holds none of a query's keys (m = -inf, l = 0): the combine kernels skip it
+__device__ __forceinline__ void store_empty_partial(float* part) {
+  if (threadIdx.x < 64) part[threadIdx.x] = 0.f;
+  if (threadIdx.x == 0) {
+    part[64] = -INFINITY;
+    part[65] = 0.f;
+  }
+}
+
+// multi-query calls: the query rows of one (clip, head) and the grouping of the queries that share a key start
+struct MqP {
+  int64_t sqq, soq;
+  int nq, causal;
+};
+template <int QN>
+__device__ __forceinline__ void mq_group(unsigned& pend, const int (&lo)[QN], const int (&hi)[QN], int& glo,
+                                         int (&ghi)[QN]) {
+  bool found = false;
+  glo = 0;
+#pragma unroll
+  for (int j = 0; j < QN; ++j)
+    if (!found && ((pend >> j) & 1u)) { glo = lo[j]; found = true; }
+#pragma unroll
+  for (int j = 0; j < QN; ++j) {
+    const bool in = ((pend >> j) & 1u) && lo[j] == glo;
+    ghi[j] = in ? hi[j] : glo;
+    if (in) pend &= ~(1u << j);
+  }
+}
+
+// The checks the decode-attention entry points share (statuses as include/tw_hip.h lists them) and the DecP of the
+// call.  tk_last: the most keys a query of a fixed-Tk call attends.  K / V strides count K / V elements.
+inline int dec_fill(DecP& p, const void* q, int64_t sqb, const void* k, int64_t ldk, int64_t skb, int64_t hsk,
+                    const void* v, int64_t ldv, int64_t svb, int64_t hsv, void* o, int64_t sob, int H, int Tk,
+                    int tk_last, const int* tk_dev, const int* k_start, float scale) {
+  if ((!tk_dev && Tk <= 0) || tk_last > DA_MAX_TK) return TW_EUNSUPPORTED;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return TW_EINVAL;
+  if ((sqb | ldk | skb | ldv | svb | hsk | hsv) & 7) return TW_EINVAL;
+  if (skb < 0 || svb < 0 || hsk < 0 || hsv < 0) return TW_EINVAL;
+  p.q = q; p.sqb = sqb;
+  p.k = k; p.ldk = ldk; p.skb = skb;
+  p.v = v; p.ldv = ldv; p.svb = svb;
+  p.o = o; p.sob = sob;
+  p.hsk = hsk; p.hsv = hsv;
+  p.H = H; p.Tk = Tk; p.tk_dev = tk_dev; p.k_start = k_start; p.c = scale * 1.4426950408889634f;
+  return TW_OK;
+}
+// fixed-Tk calls on few (clip, head) pairs split the keys into chunks of DA_SPLIT
+inline bool dec_split(const int* tk_dev, int pairs, int nchunk) {
+  return !tk_dev && pairs < 640 && nchunk >= 2 && nchunk <= DA_MAX_CHUNK;
+}
 
 }  // namespace twd

@@ -79,6 +79,12 @@ SIGNATURES = {
     "tw_kv_append": [P, I64, P, I64, I64, I32, I32, I32, P, P],
     "tw_kv_head_major": [P, I64, P, I32, I32, I32, I32, P],
     "tw_step_advance": [P, I32, P],
+    # 8-bit cross-attention K/V cache (cross_kv_dtype="fp8_e4m3"): quantiser and the decode attention over it
+    "tw_kv_head_major_fp8": [P, I64, P, P, I32, I32, I32, I32, P],
+    "tw_decode_attn_fp8": [P, I64, P, I64, I64, I64, P, I64, I64, I64, P, P, I64, P, I64, I32, I32, I32, P, P, I32,
+                           F32, I32, P],
+    "tw_decode_attn_mq_fp8": [P, I64, I64, P, I64, I64, I64, P, I64, I64, I64, P, P, I64, P, I64, I64, I32, I32, I32,
+                              I32, P, P, I32, I32, F32, I32, P],
     # fp16 arithmetic path (torch_dtype=float16 decode: run_eval.py:99, run_pseudo_labelling.py:461-463)
     "tw_gemm_f16": [P, I64, I32, P, I64, I32, P, I64, I32, I32, I32, I32, I32, I64, I64, I64, F32, P,
                     P, I64, I64, I32, I32, P, I64, I64, I32, P],

@@ -15,7 +15,9 @@ Device layout (one DecodeSession per batch of clips):
     column when the prompts are left-padded; tw_decode_attn_mq for the Q rows of a verify pass);
   * cross-attention K/V per decoder layer: bf16, head-major (K [B][H][1500][64] then V), projected
     once from the encoder output (k has no bias: the zero-bias segment of the fused KV bias) and
-    transposed by tw_kv_head_major;
+    transposed by tw_kv_head_major; with model.cross_kv_dtype == "fp8_e4m3" the same blocks as e4m3 bytes plus
+    one fp32 power-of-two scale per (clip, head) block of K and of V (tw_kv_head_major_fp8), read by
+    tw_decode_attn_fp8 / tw_decode_attn_mq_fp8;
   * logits bf16 [B][Vp]; tw_greedy_select applies the suppress masks, takes the argmax, writes
     the token into the id matrix and the next step's input vector, and tracks finished rows.
 Everything runs on the HIP library.  The step index lives in device memory (t_dev: embedding
@@ -75,8 +77,15 @@ class DecodeSession:
         # cross-attention K/V head-major (K [B][H][Tk][64] then V): each (clip, head) of the per-step
         # cross-attention reads two contiguous runs instead of 128-B rows 2d apart (tw_kv_head_major; the
         # projection goes through one scratch [B*Tk][2d] block)
-        self.cross_kv = [torch.empty(2 * B * self.H * Tk * 64, dtype=act, device=dev)
+        # model.cross_kv_dtype == "fp8_e4m3": the same blocks as e4m3 bytes, half the size, with one fp32 power-of-two
+        # scale per (clip, head) block of K and of V (tw_kv_head_major_fp8; the format: include/tw_hip.h).  The scale
+        # tensors (2*B*H floats per layer, K's then V's) are allocated once, so a captured step survives set_encoder
+        self.xkv_dtype = getattr(model, "cross_kv_dtype", None)
+        self.xkv_fp8 = self.xkv_dtype == "fp8_e4m3"
+        self.cross_kv = [torch.empty(2 * B * self.H * Tk * 64, dtype=torch.uint8 if self.xkv_fp8 else act, device=dev)
                          for _ in range(cfg.decoder_layers)]
+        self.cross_scale = [torch.ones(2 * B * self.H, dtype=torch.float32, device=dev)
+                            for _ in range(cfg.decoder_layers)] if self.xkv_fp8 else None
         self.graph = None
         self.xkv_shared = False
         self.set_encoder(enc16)
@@ -125,7 +134,10 @@ class DecodeSession:
             wkv = m.wspan(p + ".k_proj.weight", p + ".v_proj.weight", (2 * d, d))
             bkv = m.wspan(p + ".k_proj.zero_bias", p + ".v_proj.bias", (2 * d,))
             m._lin(enc16, wkv, bkv, proj)
-            F.kv_head_major(proj, 2 * d, kv, nb, self.Tk, self.H)
+            if self.xkv_fp8:        # the same 16-bit projection, then quantised per (clip, head) block
+                F.kv_head_major_fp8(proj, 2 * d, kv, self.cross_scale[i], nb, self.Tk, self.H)
+            else:
+                F.kv_head_major(proj, 2 * d, kv, nb, self.Tk, self.H)
         del proj
 
     def set_pads(self, pads, shift_positions=False):
@@ -187,8 +199,8 @@ class DecodeSession:
     def _layers(self, b, sb, rows, self_attn, cross_attn, head=True):
         """The decoder layers and the head on the b.M rows embedded in b.x: per layer the fused QKV, k and v to the
         cache (row m of b to cache row *t_dev of the block m * sb elements in; `rows` bounds that row), self_attn(b,
-        cache) into b.o, out-proj, cross-q, cross_attn(b, kv) into b.o, out-proj, MLP.  head=False stops after the
-        last layer."""
+        cache) into b.o, out-proj, cross-q, cross_attn(b, layer index) into b.o, out-proj, MLP.  head=False stops
+        after the last layer."""
         m, d, t_dev = self.m, self.d, self.t_dev
         x, o, y = b.x, b.o, b.y
         for i in range(m.config.decoder_layers):
@@ -207,7 +219,7 @@ class DecodeSession:
             # cross attention over the encoder frames
             self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
                          m._w16(p + ".encoder_attn.q_proj.bias"), b.q, y)
-            cross_attn(b, self.cross_kv[i])
+            cross_attn(b, i)
             self._lin(o, m._w16(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"), x,
                       res=x)
             # MLP
@@ -231,8 +243,13 @@ class DecodeSession:
         F.decode_attn_mq(b.qkv, Q * 3 * d, 3 * d, cache, 2 * d, 0, cache.view(-1)[d:], 2 * d, 0, b.o, Q * d, d,
                          1, self.H, Q, 1, 0.125, tk_dev=self.t_dev, tk_max=self.T_max, causal=True)
 
-    def _cross_attn_mq(self, b, kv):        # the clip's [H][Tk][64] K then V blocks
-        d, Q, n1 = self.d, b.M, self.H * self.Tk * 64
+    def _cross_attn_mq(self, b, i):         # the clip's [H][Tk][64] K then V blocks of layer i
+        d, Q, n1, kv = self.d, b.M, self.H * self.Tk * 64, self.cross_kv[i]
+        if self.xkv_fp8:
+            s = self.cross_scale[i]
+            F.decode_attn_mq_fp8(b.q, Q * d, d, kv, 64, 0, kv[n1:], 64, 0, s, s[self.H:], 0, b.o, Q * d, d, 1, self.H,
+                                 Q, self.Tk, 0.125, hsk=self.Tk * 64, hsv=self.Tk * 64)
+            return
         F.decode_attn_mq(b.q, Q * d, d, kv, 64, 0, kv[n1:], 64, 0, b.o, Q * d, d, 1, self.H, Q, self.Tk, 0.125,
                          hsk=self.Tk * 64, hsv=self.Tk * 64)
 
@@ -262,9 +279,17 @@ class DecodeSession:
         F.decode_attn(b.qkv, 3 * d, cache, 2 * d, sb, cache.view(-1)[d:], 2 * d, sb, b.o, d, self.B, self.H, 1, 0.125,
                       tk_dev=self.t_dev, tk_max=self.T_max, k_start=self.k_start if self.padded else None)
 
-    def _cross_attn(self, b, kv):
-        B, H, Tk, d = self.B, self.H, self.Tk, self.d
-        if self.xkv_shared:     # every row over the one clip's [H][Tk][64] blocks (batch stride 0)
+    def _cross_attn(self, b, i):
+        B, H, Tk, d, kv = self.B, self.H, self.Tk, self.d, self.cross_kv[i]
+        if self.xkv_fp8:        # the same two calls over bytes, with the blocks' scales (K's, then V's)
+            s = self.cross_scale[i]
+            if self.xkv_shared:
+                F.decode_attn_fp8(b.q, d, kv, 64, 0, kv[H * Tk * 64:], 64, 0, s, s[H:], 0, b.o, d, B, H, Tk, 0.125,
+                                  hsk=Tk * 64, hsv=Tk * 64)
+            else:
+                F.decode_attn_fp8(b.q, 64, kv, 64, Tk * 64, kv[B * H * Tk * 64:], 64, Tk * 64, s, s[B * H:], 1, b.o,
+                                  64, B * H, 1, Tk, 0.125)
+        elif self.xkv_shared:   # every row over the one clip's [H][Tk][64] blocks (batch stride 0)
             F.decode_attn(b.q, d, kv, 64, 0, kv[H * Tk * 64:], 64, 0, b.o, d, B, H, Tk, 0.125, hsk=Tk * 64,
                           hsv=Tk * 64)
         else:                   # B*H one-head clips over contiguous [Tk][64] runs
@@ -452,7 +477,8 @@ class _PromptedDecode:
 
     def _open(self, sess, model, enc, Tk, spare=0):
         """The session of `model` over this window's encoder rows: built on first use, re-projected in place after."""
-        if sess is None:
+        # the K/V format is the session's for life
+        if sess is None or sess.xkv_dtype != getattr(model, "cross_kv_dtype", None):
             return DecodeSession(model, enc, self.B, Tk, self.T_max, spare=spare)
         sess.set_encoder(enc)
         return sess
@@ -1124,8 +1150,9 @@ class _LongForm:
     decoders: dict = dataclasses.field(default_factory=dict)
 
     def decoder(self, P, ml, nb=1, spec=False):
-        # the two repeat options are baked into a captured step
-        key = (P, ml, nb, spec, self.rq.repetition_penalty, self.rq.no_repeat_ngram_size)
+        # the two repeat options and the models' cross-attention K/V format are baked into a captured step
+        key = (P, ml, nb, spec, self.rq.repetition_penalty, self.rq.no_repeat_ngram_size,
+               getattr(self.model, "cross_kv_dtype", None), getattr(self.rq.assistant, "cross_kv_dtype", None))
         if key in self.decoders:
             self.decoders[key] = self.decoders.pop(key)      # most recently used last
         else:

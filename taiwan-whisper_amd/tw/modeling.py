@@ -277,6 +277,8 @@ class WhisperForConditionalGeneration:
             raise ValueError("a torch_dtype=float16 model computes in fp16 only")
         if self.dtype == torch.bfloat16 and compute == "fp16":
             raise ValueError("fp16 arithmetic needs fp16 parameters or an fp32 master (fp16 autocast)")
+        if compute == "fp32" and getattr(self, "_cross_kv_dtype", None) is not None:
+            raise ValueError("cross_kv_dtype='fp8_e4m3' is set: the fp32 path keeps its K/V exact (set it to None first)")
         self.compute = compute
         # fp32-master model: the 16-bit mirror is autocast's weight cast, in the autocast dtype
         half = torch.float16 if compute == "fp16" else torch.bfloat16
@@ -290,6 +292,26 @@ class WhisperForConditionalGeneration:
         """dtype of every GEMM / attention operand and output: bf16 under autocast, fp32 on the fp32 path, fp16 for
         an fp16 model."""
         return {"fp32": torch.float32, "fp16": torch.float16}.get(self.compute, torch.bfloat16)
+
+    CROSS_KV_DTYPES = (None, "auto", "fp8_e4m3")
+
+    @property
+    def cross_kv_dtype(self):
+        """Format of the cross-attention K/V cache of every DecodeSession built for this model (greedy, beam,
+        long-form, the verify pass of assisted decoding, detect_language): None = the activation dtype;
+        "fp8_e4m3" = OCP e4m3 bytes with one power-of-two fp32 scale per (clip, head) block of K and of V
+        (include/tw_hip.h): half the memory and half the bytes read per generated token.  A deployment setting, like
+        a serving stack's KV-cache dtype: sessions are built per generate call, so the next call follows it."""
+        return getattr(self, "_cross_kv_dtype", None)
+
+    @cross_kv_dtype.setter
+    def cross_kv_dtype(self, value):
+        if value not in self.CROSS_KV_DTYPES:
+            raise ValueError(f"cross_kv_dtype must be None, 'auto' or 'fp8_e4m3', got {value!r}")
+        value = None if value == "auto" else value
+        if value is not None and self.compute == "fp32":
+            raise ValueError("cross_kv_dtype='fp8_e4m3' needs a 16-bit compute path: compute='fp32' exists for exactness")
+        self._cross_kv_dtype = value
 
     def act_grad(self, g: torch.Tensor) -> torch.Tensor:
         """gradient entering a GEMM: rounded to the autocast dtype (the grad of a bf16 / fp16 activation),
@@ -364,7 +386,7 @@ class WhisperForConditionalGeneration:
 
     @classmethod
     def from_pretrained(cls, path, torch_dtype=None, attn_implementation=None, low_cpu_mem_usage=True, config=None,
-                        device="cuda", compute="bf16", **kw):
+                        device="cuda", compute="bf16", cross_kv_dtype=None, **kw):
         from safetensors.torch import load_file
         cfg = config if config is not None else WhisperConfig.from_pretrained(path)
         if isinstance(cfg, dict):
@@ -372,6 +394,7 @@ class WhisperForConditionalGeneration:
         sd = load_file(os.path.join(path, "model.safetensors"))
         dt = torch_dtype or torch.float32
         m = cls.from_state_dict(cfg, sd, dtype=dt, device=device, compute="fp16" if dt == torch.float16 else compute)
+        m.cross_kv_dtype = cross_kv_dtype
         gp = os.path.join(path, "generation_config.json")
         if os.path.exists(gp):
             with open(gp) as f:

@@ -808,6 +808,69 @@ def kv_head_major(src, ld, dst, B, Tk, H):
     call("tw_kv_head_major", src.data_ptr(), ld, dst.data_ptr(), B, Tk, H, _dt(src), _stream())
 
 
+FP8_BYTES = (torch.uint8, torch.float8_e4m3fn)     # what an 8-bit K/V buffer may be typed as: one byte an element
+
+
+def kv_head_major_fp8(src, ld, dst, scales, B, Tk, H):
+    """Row-interleaved 16-bit cross K/V [B*Tk][ld] -> head-major e4m3 bytes K [B][H][Tk][64] then V, and the 2*B*H
+    fp32 block scales, K's then V's (tw_kv_head_major_fp8; the format: include/tw_hip.h)."""
+    assert src.dtype in HALF and dst.dtype in FP8_BYTES and scales.dtype == torch.float32
+    _need(src, (B * Tk - 1) * ld + 2 * 64 * H, "kv_head_major_fp8 src")
+    _need(dst, 2 * B * H * Tk * 64, "kv_head_major_fp8 dst")
+    _need(scales, 2 * B * H, "kv_head_major_fp8 scales")
+    call("tw_kv_head_major_fp8", src.data_ptr(), ld, dst.data_ptr(), scales.data_ptr(), B, Tk, H, _dt(src), _stream())
+
+
+def _decode_attn_fp8_args(what, q, sqb, sqq, k, ldk, skb, v, ldv, svb, ks, vs, ssb, o, sob, soq, B, H, Q, rows, hsk,
+                          hsv, k_start):
+    """The checks decode_attn_fp8 and decode_attn_mq_fp8 share (rows None: a call the library refuses, no extents).
+    Returns (head strides of K and V in bytes, algorithmic bytes: every K and V byte of the rows attended once)."""
+    assert q.dtype in HALF and o.dtype == q.dtype and k.dtype in FP8_BYTES and v.dtype in FP8_BYTES
+    assert ks.dtype == torch.float32 and vs.dtype == torch.float32
+    if k_start is not None:
+        assert k_start.dtype == torch.int32 and k_start.is_contiguous() and k_start.device == q.device
+        _need(k_start, B, f"{what} k_start")
+    hk, hv = (64 if hsk is None else int(hsk)), (64 if hsv is None else int(hsv))
+    if rows is None:
+        return hk, hv, 0
+    _need(q, (B - 1) * sqb + (Q - 1) * sqq + H * 64, f"{what} q")
+    _need(k, (B - 1) * skb + (rows - 1) * ldk + (H - 1) * hk + 64, f"{what} k")
+    _need(v, (B - 1) * svb + (rows - 1) * ldv + (H - 1) * hv + 64, f"{what} v")
+    _need(ks, (B - 1) * ssb + H, f"{what} k_scale")
+    _need(vs, (B - 1) * ssb + H, f"{what} v_scale")
+    _need(o, (B - 1) * sob + (Q - 1) * soq + H * 64, f"{what} o")
+    return hk, hv, 2 * B * rows * H * 64
+
+
+def decode_attn_fp8(q, sqb, k, ldk, skb, v, ldv, svb, k_scale, v_scale, ssb, o, sob, B, H, Tk, scale, hsk=None,
+                    hsv=None, k_start=None):
+    """decode_attn over an 8-bit K/V cache (tw_decode_attn_fp8): k / v are e4m3 bytes (strides in bytes), block
+    (b, h) scaled by k_scale[b*ssb + h] / v_scale[b*ssb + h]; skb = svb = ssb = 0 shares one clip's blocks.  Fixed
+    Tk only."""
+    hk, hv, work = _decode_attn_fp8_args("decode_fp8", q, sqb, 0, k, ldk, skb, v, ldv, svb, k_scale, v_scale, ssb, o,
+                                         sob, 0, B, H, 1, Tk if B > 0 and H > 0 else None, hsk, hsv, k_start)
+    fn = lambda: call("tw_decode_attn_fp8", q.data_ptr(), sqb, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv, svb, hv,
+                      k_scale.data_ptr(), v_scale.data_ptr(), ssb, o.data_ptr(), sob, B, H, Tk, None, _ptr(k_start),
+                      64, float(scale), _dt(q), _stream())
+    KernelTimer.wrap("decode_attn_cross_fp8", work, fn)
+    return o
+
+
+def decode_attn_mq_fp8(q, sqb, sqq, k, ldk, skb, v, ldv, svb, k_scale, v_scale, ssb, o, sob, soq, B, H, Q, Tk, scale,
+                       hsk=None, hsv=None, k_start=None, causal=False):
+    """decode_attn_mq over an 8-bit K/V cache (tw_decode_attn_mq_fp8), as decode_attn_fp8.  Fixed Tk only."""
+    rows = None
+    if 1 <= Q <= MQ_MAX and B > 0 and H > 0:
+        rows = Tk + (Q - 1 if causal else 0)
+    hk, hv, work = _decode_attn_fp8_args("decode_mq_fp8", q, sqb, sqq, k, ldk, skb, v, ldv, svb, k_scale, v_scale,
+                                         ssb, o, sob, soq, B, H, Q, rows, hsk, hsv, k_start)
+    fn = lambda: call("tw_decode_attn_mq_fp8", q.data_ptr(), sqb, sqq, k.data_ptr(), ldk, skb, hk, v.data_ptr(), ldv,
+                      svb, hv, k_scale.data_ptr(), v_scale.data_ptr(), ssb, o.data_ptr(), sob, soq, B, H, Q, Tk, None,
+                      _ptr(k_start), int(bool(causal)), 64, float(scale), _dt(q), _stream())
+    KernelTimer.wrap("decode_attn_mq_cross_fp8", work, fn)
+    return o
+
+
 def step_advance(t_dev, by=1):
     assert t_dev.dtype == torch.int32 and t_dev.is_cuda
     call("tw_step_advance", t_dev.data_ptr(), int(by), _stream())

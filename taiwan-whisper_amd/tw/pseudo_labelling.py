@@ -65,6 +65,9 @@ def parse_args(argv=None):
                     help="penalty on tokens already in the decoder row (> 1 penalises; 1.0: off)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0,
                     help="no n-gram of this size may occur twice in the decoder row (0: off)")
+    ap.add_argument("--cross_kv_dtype", type=str, default="auto", choices=["auto", "fp8_e4m3"],
+                    help="cross-attention K/V cache: auto -> the compute type's 16 bits; fp8_e4m3 -> 8-bit blocks with "
+                         "power-of-two scales (half the memory and bytes per token; not with float32)")
     return ap.parse_args(argv)
 
 
@@ -262,7 +265,8 @@ def main(argv=None):
     dtype = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[compute]
     model = WhisperForConditionalGeneration.from_pretrained(
         args.model_size_or_path, torch_dtype=dtype, device=torch.device("cuda", local), compute=compute)
-    print(f"Using device: cuda:{local} ({compute})", flush=True)
+    model.cross_kv_dtype = args.cross_kv_dtype
+    print(f"Using device: cuda:{local} ({compute}, cross K/V {args.cross_kv_dtype})", flush=True)
     decode = load_text_decoder(args)
     tr = ChunkTranscriber(model, args.language, args.max_new_tokens, repetition_penalty=args.repetition_penalty,
                           no_repeat_ngram_size=args.no_repeat_ngram_size)
