@@ -137,6 +137,29 @@ int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K, int64_t ld
                            int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
                            const int* offk, int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
                            float scale, float* workspace, tw_stream_t stream);
+/* The packed entries with a query-block list: the same arguments and results as the _varlen entries, and `blocks`,
+ * one of the two lists of tw_pack_blocks (list 0 with dense keys, list 1 for the causal call with offk), with its
+ * length nblk.  The forward and dQ launch one workgroup per (entry, head); dK / dV keep their key-side grid.  No
+ * workgroup is launched for rows that no clip has, and every row's bits are those of the _varlen entries.  blocks
+ * must be 16-byte aligned. */
+int tw_attn_fwd_blocks(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
+                       int64_t ldo, float* lse, const int* offq, const int* offk, const int* blocks, int nblk,
+                       int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                       tw_stream_t stream);
+int tw_attn_fwd_blocks_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv, void* O,
+                           int64_t ldo, float* lse, const int* offq, const int* offk, const int* blocks, int nblk,
+                           int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal, float scale,
+                           tw_stream_t stream);
+int tw_attn_bwd_blocks(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                       const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                       int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq, const int* offk,
+                       const int* blocks, int nblk, int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
+                       float scale, float* workspace /* H*Mq floats */, tw_stream_t stream);
+int tw_attn_bwd_blocks_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                           const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                           int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
+                           const int* offk, const int* blocks, int nblk, int B, int H, int Mq, int max_q, int Tk,
+                           int head_dim, int causal, float scale, float* workspace, tw_stream_t stream);
 
 /* Fused CE + temperature KL loss and its logits gradient (replaces run_distillation.py:1507-1516,
  * :1539-1549 and HF CE :1082-1087).  out3 = [loss, ce, kl*T^2]; dlogits (same dtype as the logits:
@@ -177,6 +200,12 @@ int tw_embed_bwd(const int64_t* ids, const float* dh, float* dE, int rows, int D
  * tw_pos_grad_rows: gP[t] += sum over clips b with t < n_b of dx[off[b] + t] (fp32, clips in ascending order);
  * max_rows = the longest clip. */
 int tw_pack_plan(const int64_t* labels, int B, int T, int* off, int64_t* src_rows, tw_stream_t stream);
+/* The query blocks of packed rows, for tw_attn_*_blocks.  A block is 128 consecutive rows of one clip (the clip's last
+ * block: what is left); from off [B+1] (max_rows >= the longest clip) two lists of the same blocks, entries of four
+ * int32 {clip, first row, rows, tiles}: list 0 at blocks (dense keys; tiles = 0), list 1 at blocks + 4*cap (causal;
+ * tiles = the 64-key tiles the block walks).  Order: descending tiles, ties by (clip, block).  *nblk = the number
+ * of blocks.  cap >= B * ceil(max_rows / 128); blocks 16-byte aligned.  Deterministic (ranks, no atomics). */
+int tw_pack_blocks(const int* off, int B, int max_rows, int* blocks, int cap, int* nblk, tw_stream_t stream);
 int tw_embed_fwd_rows(const int64_t* ids, const int64_t* src_rows, const void* tok, int tok_dtype, const void* pos,
                       int pos_dtype, void* out, int out_dtype, int rows, int T, int pos_offset, int D,
                       tw_stream_t stream);

@@ -20,7 +20,9 @@
 // share is written once: attn_frame() (the workgroup's clip, head, rows and base pointers), stage_kv(), causal_nkt(),
 // hidden() (the mask), store4() and zero().  Each kernel keeps its own pipeline.  On the host one attn_fill() builds
 // the AttnP of a dense or packed call, attn_check() decides its status, TW_DISPATCH_HVL picks the instantiation and
-// attn_fwd() / attn_bwd() launch; the eight C entries forward to those.
+// attn_fwd() / attn_bwd() launch; the twelve C entries forward to those.  The packed kernels run either on a padded
+// grid (the _varlen entries) or one workgroup per (entry, head) of a query-block list (the _blocks entries:
+// place_entry(), tw_pack_blocks in misc.hip).
 #include "common.h"
 
 #include <cstdlib>
@@ -112,6 +114,9 @@ struct AttnP {
   // lse and Dv are then [H][Mq] (Mq = offq[B], every packed query row): entry h*Mq + offq[b] + q.
   const int* offq; const int* offk;
   int Mq;
+  // The query-block list of a packed launch (tw_pack_blocks: one {clip, first row, rows, tiles} entry per 128-row
+  // block that has rows), or null: the padded grid of the entries without a list, and of every dK/dV launch.
+  const int4* wl;
 };
 
 // rows of clip b: dense [b*T, b*T + T), or [off[b], off[b+1]) of a packed matrix
@@ -163,8 +168,36 @@ struct Frame {
   }
 };
 
-// A VL kernel leaves when blk is past its clip's last row (blk >= Tq, or Tk in dK/dV): that test is workgroup-uniform
-// (blk, Tq and Tk depend on the block index only) and must stay ahead of any LDS-DMA or barrier.
+// Placement of a (heads, list entries) grid, bijective: (entry, head) of this workgroup.  Workgroup bid runs on XCD
+// bid % 8, in bid order.
+// Dense keys (cross-attention; the list is in (clip, block) order and every entry walks the same tiles): remap_bh with
+// the heads as the inner index, so XCD x takes a contiguous run of entries with all their heads and the blocks of one
+// clip, neighbours in the list, read that clip's K/V through one L2.
+// Causal (the list is in descending tile order): entry i goes to XCD i % 8 with all its heads, so every XCD walks
+// its own descending sequence (longest first) and the eight carry the same load; a clip's K/V there is at most 7
+// tiles.  The last nent % 8 entries have no residue class of their own and take the remaining workgroups in order.
+__device__ __forceinline__ void place_entry(bool causal, int& ent, int& h) {
+  if (!causal) {
+    remap_bh(h, ent);
+    return;
+  }
+  const int H = gridDim.x, nent = gridDim.y;
+  const int bid = blockIdx.y * H + blockIdx.x;
+  const int full = nent & ~7;
+  if (bid < full * H) {
+    const int t = bid >> 3;
+    h = t % H;
+    ent = (t / H) * 8 + (bid & 7);
+  } else {
+    const int local = bid - full * H, r = nent - full;
+    ent = full + local % r;
+    h = local / r;
+  }
+}
+
+// A VL kernel on the padded grid leaves when blk is past its clip's last row (blk >= Tq, or Tk in dK/dV): that test is
+// workgroup-uniform (blk, Tq and Tk depend on the block index only) and must stay ahead of any LDS-DMA or barrier.
+// With a list (AttnP::wl) every workgroup has rows.
 template <bool VL>
 __device__ __forceinline__ Frame attn_frame(const AttnP& p) {
   Frame f;
@@ -172,11 +205,20 @@ __device__ __forceinline__ Frame attn_frame(const AttnP& p) {
   f.wave = wave_id_uniform();
   f.g = f.lane >> 4;
   f.li = f.lane & 15;
-  int xblk, bh;
-  remap_bh(xblk, bh);
-  const int b = bh / p.H;
-  f.h = bh % p.H;
-  f.blk = xblk * QB;
+  int b, bh = 0;
+  if (VL && p.wl) {
+    int ent;
+    place_entry(p.causal, ent, f.h);
+    const int4 e = p.wl[ent];
+    b = e.x;
+    f.blk = e.y;
+  } else {
+    int xblk;
+    remap_bh(xblk, bh);
+    b = bh / p.H;
+    f.h = bh % p.H;
+    f.blk = xblk * QB;
+  }
   f.row = f.blk + f.wave * QW;
   f.Tq = p.Tq;
   f.Tk = p.Tk;
@@ -224,8 +266,9 @@ __device__ __forceinline__ bool hidden(const AttnP& p, const Frame& f, int q, in
 // K/V arrive in a 3-deep LDS ring: two tiles in flight (prefetch distance 2: the DMA of tile kt+2 overlaps the
 // compute of tiles kt and kt+1), counted vmcnt + a raw s_barrier (a __syncthreads() would drain every DMA in
 // flight).  (Round 3's opt-in lazy max and the 2-stage ring were deleted in round 4: DESIGN.md, Attention.)
-// VL: packed rows (AttnP::offq / offk); the grid spans the longest clip and a block past its clip's last query
-// leaves at once (workgroup-uniform, before any LDS-DMA or barrier)
+// VL: packed rows (AttnP::offq / offk); without a block list the grid spans the longest clip and a block past its
+// clip's last query leaves at once (workgroup-uniform, before any LDS-DMA or barrier); with one (AttnP::wl) every
+// workgroup has rows
 template <bool H, bool VL>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p) {
   constexpr int ST = 3;
@@ -662,24 +705,54 @@ int attn_check(const AttnP& p, int head_dim, bool packed, bool bwd) {
 
 dim3 attn_grid(const AttnP& p, int rows) { return dim3((rows + QB - 1) / QB, p.B * p.H); }
 
+// The query blocks of a packed call with a list (the _blocks entries): the list in the order of the call's kind
+// (tw_pack_blocks) and its length.  No list (dense calls, the _varlen entries): null, 0.
+struct Blocks {
+  const int* list;
+  int n;
+};
+
+// the grid of a list (place_entry): one workgroup per (head, entry)
+dim3 list_grid(const AttnP& p, const Blocks& bl) { return dim3(p.H, bl.n); }
+AttnP with_list(AttnP p, const Blocks& bl) {
+  p.wl = (const int4*)bl.list;
+  return p;
+}
+
+int blocks_check(const Blocks& bl) {
+  return bl.list != nullptr && ((uintptr_t)bl.list & 15) == 0 && bl.n >= 0 && bl.n <= 65535 ? TW_OK : TW_EINVAL;
+}
+
 // half: fp16 Q/K/V/O (HF Whisper with torch_dtype=float16: SDPA over fp16 projections, run_eval.py:99,500-509)
-int attn_fwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream) {
+// bl: the forward launches one workgroup per (entry, head) and none without rows.
+int attn_fwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream, const Blocks* bl = nullptr) {
   if (const int st = attn_check(p, head_dim, packed, false); st != ATTN_LAUNCH) return st;
+  if (bl) {
+    if (const int st = blocks_check(*bl); st != TW_OK) return st;
+    if (bl->n == 0) return TW_OK;
+  }
+  const AttnP pl = bl ? with_list(p, *bl) : p;
   TW_DISPATCH_HVL(half, packed,
-                  hipLaunchKernelGGL((attn_fwd_kernel<H, VL>), attn_grid(p, p.Tq), dim3(256), 0, stream, p));
+                  hipLaunchKernelGGL((attn_fwd_kernel<H, VL>), bl ? list_grid(p, *bl) : attn_grid(p, p.Tq), dim3(256), 0,
+                                     stream, pl));
   TW_CHECK_LAUNCH();
   return TW_OK;
 }
 
 // half: fp16 Q/K/V/O/dO/dQ/dK/dV (the student's SDPA backward under fp16 autocast, run_distillation.py:815-817
 // mixed_precision="fp16"): the bf16 kernels instantiated for fp16 words (P and dS rounded to fp16 for their MFMAs)
-int attn_bwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream) {
+int attn_bwd(const AttnP& p, int head_dim, bool packed, bool half, hipStream_t stream, const Blocks* bl = nullptr) {
   if (const int st = attn_check(p, head_dim, packed, true); st != ATTN_LAUNCH) return st;
+  if (bl)
+    if (const int st = blocks_check(*bl); st != TW_OK) return st;
   // dQ (and D, which the dK/dV kernel reads) first, then dK/dV; with packed queries and dense keys the dK/dV launch
-  // runs even when no clip has a query (zeros)
+  // runs even when no clip has a query (zeros).  With a list dQ runs one workgroup per (entry, head); dK/dV is
+  // key-side and keeps its grid.
+  const AttnP pq = bl ? with_list(p, *bl) : p;
   TW_DISPATCH_HVL(half, packed, {
-    if (p.Tq > 0)
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<H, VL>), attn_grid(p, p.Tq), dim3(256), 0, stream, p);
+    if (bl ? bl->n > 0 : p.Tq > 0)
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<H, VL>), bl ? list_grid(p, *bl) : attn_grid(p, p.Tq), dim3(256), 0,
+                         stream, pq);
     hipLaunchKernelGGL((attn_bwd_dkdv_kernel<H, VL>), attn_grid(p, p.Tk), dim3(256), 0, stream, p);
   });
   TW_CHECK_LAUNCH();
@@ -755,4 +828,47 @@ extern "C" int tw_attn_bwd_varlen_f16(const void* Q, int64_t ldq, const void* K,
   return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq, dO,
                             lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
                   head_dim, true, true, stream);
+}
+
+// The packed entries with a query-block list (tw_pack_blocks): `blocks` is the list in the order of the call's kind
+// (dense keys or causal), nblk entries.
+extern "C" int tw_attn_fwd_blocks(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                  void* O, int64_t ldo, float* lse, const int* offq, const int* offk,
+                                  const int* blocks, int nblk, int B, int H, int Mq, int max_q, int Tk, int head_dim,
+                                  int causal, float scale, hipStream_t stream) {
+  const Blocks bl = {blocks, nblk};
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq),
+                  head_dim, true, false, stream, &bl);
+}
+
+extern "C" int tw_attn_fwd_blocks_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                      int64_t ldv, void* O, int64_t ldo, float* lse, const int* offq, const int* offk,
+                                      const int* blocks, int nblk, int B, int H, int Mq, int max_q, int Tk,
+                                      int head_dim, int causal, float scale, hipStream_t stream) {
+  const Blocks bl = {blocks, nblk};
+  return attn_fwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq),
+                  head_dim, true, true, stream, &bl);
+}
+
+extern "C" int tw_attn_bwd_blocks(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V, int64_t ldv,
+                                  const void* O, int64_t ldo, const void* dO, int64_t lddo, const float* lse, void* dQ,
+                                  int64_t lddq, void* dK, int64_t lddk, void* dV, int64_t lddv, const int* offq,
+                                  const int* offk, const int* blocks, int nblk, int B, int H, int Mq, int max_q, int Tk,
+                                  int head_dim, int causal, float scale, float* workspace, hipStream_t stream) {
+  const Blocks bl = {blocks, nblk};
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, true, false, stream, &bl);
+}
+
+extern "C" int tw_attn_bwd_blocks_f16(const void* Q, int64_t ldq, const void* K, int64_t ldk, const void* V,
+                                      int64_t ldv, const void* O, int64_t ldo, const void* dO, int64_t lddo,
+                                      const float* lse, void* dQ, int64_t lddq, void* dK, int64_t lddk, void* dV,
+                                      int64_t lddv, const int* offq, const int* offk, const int* blocks, int nblk,
+                                      int B, int H, int Mq, int max_q, int Tk, int head_dim, int causal,
+                                      float scale, float* workspace, hipStream_t stream) {
+  const Blocks bl = {blocks, nblk};
+  return attn_bwd(attn_fill(Q, ldq, K, ldk, V, ldv, O, ldo, lse, B, H, max_q, Tk, causal, scale, offq, offk, Mq, dO,
+                            lddo, dQ, lddq, dK, lddk, dV, lddv, workspace),
+                  head_dim, true, true, stream, &bl);
 }

@@ -54,6 +54,45 @@ __global__ __launch_bounds__(1024) void pack_plan_kernel(const int64_t* __restri
   for (int64_t i = off[B] + threadIdx.x; i < (int64_t)B * T; i += 1024) src[i] = 0;
 }
 
+// The query blocks of packed rows for the attention kernels (attention.hip, AttnP::wl).  A block is 128 consecutive
+// rows of one clip, the last block of a clip what is left; block k of clip b exists when k*128 < n_b.  Two lists of
+// the same blocks, `cap` int4 entries apart, each entry {clip, first row, rows, tiles}:
+//   list 0 (dense keys, cross-attention: every block walks the same keys), tiles = 0;
+//   list 1 (causal self-attention), tiles = the 64-key tiles the block walks, ceil(min(n_b, first row + 128) / 64).
+// The order is descending tiles, ties by (clip, block): in list 0 that is (clip, block) order.  *nblk is the number of
+// blocks.  An entry's place is its rank, counted over all blocks by every thread that owns one: no atomics, the same
+// list on every run.
+__global__ __launch_bounds__(1024) void pack_blocks_kernel(const int* __restrict__ off, int B, int max_rows,
+                                                           int4* __restrict__ blocks, int cap, int* nblk) {
+  const int mb = (max_rows + 127) / 128;                  // blocks of the longest clip
+  auto key = [&](int list, int b, int k, int n) -> uint64_t {
+    const int tiles = list ? (min(n, k * 128 + 128) + 63) / 64 : 0;
+    return ((uint64_t)(0xfffff - tiles) << 40) | ((uint64_t)b << 16) | (uint64_t)k;
+  };
+  for (int c = threadIdx.x; c < B * mb; c += 1024) {
+    const int b = c / mb, k = c % mb;
+    const int n = min(off[b + 1] - off[b], max_rows);
+    if (k * 128 >= n) continue;
+    const uint64_t k0 = key(0, b, k, n), k1 = key(1, b, k, n);
+    int r0 = 0, r1 = 0;
+    for (int b2 = 0; b2 < B; ++b2) {
+      const int n2 = min(off[b2 + 1] - off[b2], max_rows);
+      for (int k2 = 0; k2 * 128 < n2; ++k2) {
+        r0 += key(0, b2, k2, n2) < k0;
+        r1 += key(1, b2, k2, n2) < k1;
+      }
+    }
+    const int rows = min(128, n - k * 128);
+    if (r0 < cap) blocks[r0] = int4{b, k * 128, rows, 0};
+    if (r1 < cap) blocks[cap + r1] = int4{b, k * 128, rows, (min(n, k * 128 + 128) + 63) / 64};
+  }
+  if (threadIdx.x == 0) {
+    int nb = 0;
+    for (int b = 0; b < B; ++b) nb += (max(min(off[b + 1] - off[b], max_rows), 0) + 127) / 128;
+    *nblk = nb;
+  }
+}
+
 // embed_fwd_kernel for packed rows: row r sits at position src[r] % T of its clip
 __global__ void embed_fwd_rows_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ src,
                                       const void* __restrict__ tok, int tok_dtype, const void* __restrict__ pos,
@@ -321,6 +360,16 @@ extern "C" int tw_embed_fwd(const int64_t* ids, const void* tok, int tok_dtype, 
 extern "C" int tw_pack_plan(const int64_t* labels, int B, int T, int* off, int64_t* src_rows, hipStream_t stream) {
   if (B <= 0 || T <= 0) return TW_EINVAL;
   hipLaunchKernelGGL(pack_plan_kernel, dim3(1), dim3(1024), 0, stream, labels, B, T, off, src_rows);
+  TW_CHECK_LAUNCH();
+  return TW_OK;
+}
+
+extern "C" int tw_pack_blocks(const int* off, int B, int max_rows, int* blocks, int cap, int* nblk,
+                              hipStream_t stream) {
+  if (B <= 0 || max_rows < 0 || !off || !blocks || !nblk || ((uintptr_t)blocks & 15) ||
+      (int64_t)cap < (int64_t)B * ((max_rows + 127) / 128))
+    return TW_EINVAL;
+  hipLaunchKernelGGL(pack_blocks_kernel, dim3(1), dim3(1024), 0, stream, off, B, max_rows, (int4*)blocks, cap, nblk);
   TW_CHECK_LAUNCH();
   return TW_OK;
 }

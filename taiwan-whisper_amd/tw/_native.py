@@ -38,7 +38,16 @@ SIGNATURES = {
                            I32, I32, I32, I32, F32, P, P],
     "tw_attn_bwd_varlen_f16": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, P, P, I32, I32,
                                I32, I32, I32, I32, I32, F32, P, P],
+    # ... with a query-block list (tw_pack_blocks): blocks, nblk after offk
+    "tw_attn_fwd_blocks": [P, I64, P, I64, P, I64, P, I64, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32, P],
+    "tw_attn_fwd_blocks_f16": [P, I64, P, I64, P, I64, P, I64, P, P, P, P, I32, I32, I32, I32, I32, I32, I32, I32, F32,
+                               P],
+    "tw_attn_bwd_blocks": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, P, P, P, I32, I32, I32,
+                           I32, I32, I32, I32, I32, F32, P, P],
+    "tw_attn_bwd_blocks_f16": [P, I64, P, I64, P, I64, P, I64, P, I64, P, P, I64, P, I64, P, I64, P, P, P, I32, I32,
+                               I32, I32, I32, I32, I32, I32, F32, P, P],
     "tw_pack_plan": [P, I32, I32, P, P, P],
+    "tw_pack_blocks": [P, I32, I32, P, I32, P, P],
     "tw_embed_fwd_rows": [P, P, P, I32, P, I32, P, I32, I32, I32, I32, I32, P],
     "tw_pos_grad_rows": [P, P, I32, I32, I32, P, P],
     "tw_kl_ce": [P, P, I64, I32, P, I64, I32, F32, F32, F32, P, F32, P, P, P, P],

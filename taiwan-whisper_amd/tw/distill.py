@@ -227,11 +227,15 @@ class DistillationTrainer:
         tw_pack_plan are copied to pinned memory asynchronously and the callable waits for that copy -- call it after
         the encoder forward has been queued, so the GPU has that work while the host waits."""
         B, T = labels.shape
-        off = torch.empty(B + 1, dtype=torch.int32, device=labels.device)
+        # off [B+1] and the length of the attention's query-block lists in one buffer: one copy to the host
+        plan = torch.empty(B + 2, dtype=torch.int32, device=labels.device)
+        off, nblk = plan[: B + 1], plan[B + 1:]
         src = torch.empty(B * T, dtype=torch.int64, device=labels.device)
+        blocks = PackedRows.new_blocks(B, T, labels.device)
         F.pack_plan(labels, off, src)
-        def descriptor(lens):
-            pk = PackedRows(lens, off, src, T)
+        F.pack_blocks(off, B, T, blocks, nblk)
+        def descriptor(lens, nblk=None):
+            pk = PackedRows(lens, off, src, T, blocks, nblk)
             return pk if pk.M > 0 else None
 
         if not batch_labels.is_cuda:
@@ -240,15 +244,15 @@ class DistillationTrainer:
             return lambda: descriptor(lens)
         host = self._pin.get(B)
         if host is None:
-            host = self._pin[B] = torch.empty(B + 1, dtype=torch.int32).pin_memory()
-        host.copy_(off, non_blocking=True)
+            host = self._pin[B] = torch.empty(B + 2, dtype=torch.int32).pin_memory()
+        host.copy_(plan, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
 
         def done():
             ev.synchronize()
             o = host.tolist()
-            return descriptor([o[b + 1] - o[b] for b in range(B)])
+            return descriptor([o[b + 1] - o[b] for b in range(B)], o[B + 1])
         return done
 
     def train_step(self, batch, temperature: Optional[float] = None, end_of_dataloader: bool = False):

@@ -48,9 +48,11 @@ def padded_vocab(V: int) -> int:
 class PackedRows:
     """Packed decoder rows: clip b keeps its rows 0 .. lens[b]-1 and the clips are concatenated, M rows
     in all, in place of the padded [B, T].  lens: host ints; off: device int32 [B+1] running sum of lens; src: device
-    int64, src[r] = b*T + t of packed row r (first M entries); T: the padded length."""
+    int64, src[r] = b*T + t of packed row r (first M entries); T: the padded length.
+    blocks: the attention's query-block lists (ops.pack_blocks over off with max_rows = T: device int32 [2][cap][4])
+    with nblk, their number, on the host; left out, both are made here from off and lens."""
 
-    def __init__(self, lens, off, src, T):
+    def __init__(self, lens, off, src, T, blocks=None, nblk=None):
         self.lens = [int(n) for n in lens]
         self.B, self.T = len(self.lens), int(T)
         self.M, self.max_len = sum(self.lens), max(self.lens, default=0)
@@ -59,6 +61,21 @@ class PackedRows:
         if off.dtype != torch.int32 or off.numel() < self.B + 1 or src.dtype != torch.int64 or src.numel() < self.M:
             raise ValueError("packed rows: off is int32 [B+1], src int64 [>= M]")
         self.off, self.src = off, src[: self.M]
+        want = sum((n + 127) // 128 for n in self.lens)
+        if blocks is None and self.M > 0:
+            blocks = self.new_blocks(self.B, self.T, off.device)
+            F.pack_blocks(off, self.B, self.T, blocks, torch.empty(1, dtype=torch.int32, device=off.device))
+        if nblk is not None and int(nblk) != want:
+            raise ValueError(f"packed rows: {nblk} blocks do not match the lengths ({want})")
+        self.blocks, self.nblk = blocks, want
+
+    @staticmethod
+    def new_blocks(B, T, device):
+        return torch.empty(2, max(B * ((T + 127) // 128), 1), 4, dtype=torch.int32, device=device)
+
+    def block_list(self, causal):
+        """The `blocks` argument of ops.attn_*_varlen: list 1 for the causal self-attention, list 0 for dense keys."""
+        return self.blocks[1 if causal else 0], self.nblk
 
     @classmethod
     def from_lens(cls, lens, T, device):
@@ -589,7 +606,8 @@ class WhisperForConditionalGeneration:
             F.attn_fwd(q, ldq, k, ldkv, v, ldkv, o, d, lse, B, H, T, T if Tk is None else Tk, causal, 0.125)
         else:       # packed queries; cross-attention runs them against each clip's dense Tk encoder rows
             offk, Tk = (pk.off, pk.max_len) if Tk is None else (None, Tk)
-            F.attn_fwd_varlen(q, ldq, k, ldkv, v, ldkv, o, d, lse, pk.off, offk, pk.B, H, M, pk.max_len, Tk, causal, 0.125)
+            F.attn_fwd_varlen(q, ldq, k, ldkv, v, ldkv, o, d, lse, pk.off, offk, pk.B, H, M, pk.max_len, Tk, causal, 0.125,
+                              blocks=pk.block_list(causal))
         out = self._res_out(o, self._w16(p + ".out_proj.weight"), self._w16(p + ".out_proj.bias"), x, tape, "attn")
         return out, o, lse
 
@@ -942,7 +960,8 @@ class Backward:
         else:       # dense keys: every clip's dK / dV block is written (zeros for a clip without rows)
             offk, Tk = (pk.off, pk.max_len) if Tk is None else (None, Tk)
             F.attn_bwd_varlen(q, ldq, k, ldkv, v, ldkv, st["o"], d, do, d, st["lse"], dq, lddq, dk, lddkv, dv, lddkv,
-                              pk.off, offk, pk.B, H, pk.M, pk.max_len, Tk, causal, 0.125)
+                              pk.off, offk, pk.B, H, pk.M, pk.max_len, Tk, causal, 0.125,
+                              blocks=pk.block_list(causal))
 
     def attn(self, p, st, dx):
         m = self.m

@@ -272,29 +272,47 @@ def attn_bwd(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, 
          float(scale), workspace.data_ptr(), _stream())
 
 
-def attn_fwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, causal, scale):
+def _block_args(sym, blocks):
+    """blocks (attn_*_varlen): None, or (list, nblk) from PackedRows.block_list -> the symbol of the entry that takes
+    the list and its two arguments."""
+    if blocks is None:
+        return sym, ()
+    wl, nblk = blocks
+    assert wl.dtype == torch.int32 and wl.is_contiguous() and wl.numel() >= 4 * nblk
+    return sym.replace("_varlen", "_blocks"), (wl.data_ptr(), int(nblk))
+
+
+def attn_fwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, lse, offq, offk, B, H, Mq, max_q, Tk, causal, scale, blocks=None):
     """attn_fwd over packed rows (16-bit only): offq [B+1] int32 device offsets of the clips' query rows, Mq their
-    total and max_q the longest; offk = offq (packed keys, Tk = max_q) or None (dense keys, Tk each).  lse [H][Mq]."""
+    total and max_q the longest; offk = offq (packed keys, Tk = max_q) or None (dense keys, Tk each).  lse [H][Mq].
+    blocks: the query-block list of the call's kind (PackedRows.block_list(causal)): only blocks that have rows are
+    launched; without it the grid spans B x the longest clip.  The results are the same bits either way."""
     sym = _attn_sym("attn_fwd_varlen", q, ((q, ldq, "q"), (o, ldo, "o")), ((k, ldk, "k"), (v, ldv, "v")), lse, H, B,
                     max_q, Tk, offq, offk, Mq)
     if sym is not None:
+        sym, bl = _block_args(sym, blocks)
         call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, _ptr(lse),
-             offq.data_ptr(), _ptr(offk), B, H, Mq, max_q, Tk, 64, int(causal), float(scale), _stream())
+             offq.data_ptr(), _ptr(offk), *bl, B, H, Mq, max_q, Tk, 64, int(causal), float(scale), _stream())
     return o
 
 
 def attn_bwd_varlen(q, ldq, k, ldk, v, ldv, o, ldo, do, lddo, lse, dq, lddq, dk, lddk, dv, lddv, offq, offk, B, H, Mq,
-                    max_q, Tk, causal, scale):
-    """attn_bwd over packed rows (see attn_fwd_varlen); with dense keys every clip's dK / dV block is written."""
+                    max_q, Tk, causal, scale, blocks=None, workspace=None):
+    """attn_bwd over packed rows (see attn_fwd_varlen); with dense keys every clip's dK / dV block is written.
+    blocks: dQ (and D) run over the list; dK / dV keep their key-side grid.  workspace: fp32 [H][Mq], receives
+    D = rowsum(dO * O)."""
     sym = _attn_sym("attn_bwd_varlen", q, ((q, ldq, "q"), (o, ldo, "o"), (do, lddo, "do"), (dq, lddq, "dq")),
                     ((k, ldk, "k"), (v, ldv, "v"), (dk, lddk, "dk"), (dv, lddv, "dv")), lse, H, B, max_q, Tk, offq,
                     offk, Mq)
     if sym is None:
         return
-    ws = torch.empty(max(H * Mq, 1), dtype=torch.float32, device=q.device)
+    sym, bl = _block_args(sym, blocks)
+    ws = workspace
+    if ws is None or ws.numel() < H * Mq:
+        ws = torch.empty(max(H * Mq, 1), dtype=torch.float32, device=q.device)
     call(sym, q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv, o.data_ptr(), ldo, do.data_ptr(), lddo,
-         lse.data_ptr(), dq.data_ptr(), lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, offq.data_ptr(), _ptr(offk), B,
-         H, Mq, max_q, Tk, 64, int(causal), float(scale), ws.data_ptr(), _stream())
+         lse.data_ptr(), dq.data_ptr(), lddq, dk.data_ptr(), lddk, dv.data_ptr(), lddv, offq.data_ptr(), _ptr(offk),
+         *bl, B, H, Mq, max_q, Tk, 64, int(causal), float(scale), ws.data_ptr(), _stream())
 
 
 def kl_ce(s_logits, t_logits, labels, V, n_valid, T=2.0, ce_w=0.8, kl_w=1.0, grad_scale=1.0, dlogits=None,
@@ -373,6 +391,17 @@ def pack_plan(labels, off, src_rows):
     assert off.dtype == torch.int32 and src_rows.dtype == torch.int64
     _need(off, B + 1, "pack_plan off"); _need(src_rows, B * T, "pack_plan src_rows")
     call("tw_pack_plan", labels.data_ptr(), B, T, off.data_ptr(), src_rows.data_ptr(), _stream())
+
+
+def pack_blocks(off, B, max_rows, blocks, nblk):
+    """off [B+1] int32 (clips of at most max_rows rows) -> the query blocks of the packed attention: blocks int32
+    [2][cap][4], entries {clip, first row, rows, tiles} (list 0: dense keys, list 1: causal; cap >= B *
+    ceil(max_rows / 128)), and nblk int32 [1], their number.  See tw_pack_blocks."""
+    assert off.dtype == torch.int32 and blocks.dtype == torch.int32 and nblk.dtype == torch.int32
+    assert blocks.dim() == 3 and blocks.shape[0] == 2 and blocks.shape[2] == 4 and blocks.is_contiguous()
+    _need(off, B + 1, "pack_blocks off"); _need(nblk, 1, "pack_blocks nblk")
+    call("tw_pack_blocks", off.data_ptr(), B, int(max_rows), blocks.data_ptr(), blocks.shape[1], nblk.data_ptr(),
+         _stream())
 
 
 def embed_fwd_rows(ids, src_rows, tok, pos, out, T, pos_offset=0):
