@@ -322,6 +322,14 @@ int tw_spec_accept(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_
                    int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a, uint8_t* done_snap, int* last_ts,
                    int* last_ts_a, int begin_col, int ts_begin, float* slots, float* sum_logp, int* hist,
                    int hist_cap, tw_stream_t stream);
+/* tw_spec_accept_lp: tw_spec_accept with tok_logp, this row of the per-token log-prob matrix (NULL: tw_spec_accept;
+ * non-NULL needs slots).  Column t+1+j takes slots[j] for each accepted j < the accepted count -- the values added to
+ * sum_logp, in the same order -- and the columns rolled back, up to t+k+1 (those refilled with eos), take 0.0f; the
+ * row holds the ids' columns (t_cap + k + 1).  Everything else is tw_spec_accept's; the same error returns. */
+int tw_spec_accept_lp(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev, int* t_dev_a,
+                      int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a, uint8_t* done_snap, int* last_ts,
+                      int* last_ts_a, int begin_col, int ts_begin, float* slots, float* sum_logp, float* tok_logp,
+                      int* hist, int hist_cap, tw_stream_t stream);
 /* tw_embed_step_multi: out[j] = tok[ids[j]] + pos[min(*t_dev + j, npos - 1)] for the Q consecutive positions of
  * one row (the verify pass; Q = 1: a step whose position is clamped to the table). */
 int tw_embed_step_multi(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype, void* out,
@@ -356,6 +364,27 @@ int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dtype, int B,
                         const uint32_t* begin_bits, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids, int col,
                         int64_t* next_ids, const int* t_dev, int begin_col, int ts_begin, int no_ts, int max_initial,
                         int* last_ts, const uint32_t* ctl, float* sum_logp, tw_stream_t stream);
+/* tw_select_sample[_ts]_lp: tw_select_sample[_ts] that also keeps the step's log-prob per column
+ * (generate(return_token_logprobs=True)).  For every row b, tok_logp[b*ld_lp + c] = the fp32 value the call adds to
+ * sum_logp[b], c the column the token goes to (col (+ *t_dev), as for ids): written for rows not yet finished, the
+ * eos step included; a row that was already finished gets 0.0f, so every generated column is written once per decode.
+ * The value is the log-softmax of the processed row at the chosen token: after the suppress and begin-suppress
+ * masks, the timestamp rules and the repeat pre-pass (tw_repeat_process), of x itself when sampling at temperature T
+ * (scores * T) -- HF's _retrieve_avg_logprobs convention, not the raw-logit one.  The row's owner thread stores
+ * it; the selection, ids, done, last_ts and sum_logp are those of tw_select_sample[_ts] on the same inputs, bit for bit, and the stored values added
+ * in column order in fp32 reproduce sum_logp.  sum_logp or tok_logp may be NULL, not both; with tok_logp NULL the
+ * call is tw_select_sample[_ts].  ld_lp >= 1 + the largest column written (checked when t_dev == NULL).  Returns 1
+ * for a bad shape or a null pointer (both of sum_logp and tok_logp among them), 2 for a dtype other than bf16 / fp16
+ * / fp32 or B, V >= 2^21; nothing is written on error. */
+int tw_select_sample_lp(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
+                        const uint32_t* begin_bits, int apply_begin, int64_t eos, uint8_t* done, int64_t* ids,
+                        int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col,
+                        const uint32_t* ctl, float* sum_logp, float* tok_logp, int64_t ld_lp, tw_stream_t stream);
+int tw_select_sample_ts_lp(const void* logits, int64_t ld, int logits_dtype, int B, int V,
+                           const uint32_t* suppress_bits, const uint32_t* begin_bits, int64_t eos, uint8_t* done,
+                           int64_t* ids, int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col,
+                           int ts_begin, int no_ts, int max_initial, int* last_ts, const uint32_t* ctl,
+                           float* sum_logp, float* tok_logp, int64_t ld_lp, tw_stream_t stream);
 int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, int V, int token, float* out,
                      tw_stream_t stream);
 /* tw_repeat_process: HF RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor (logits_process.py;

@@ -18,7 +18,9 @@
 //    not torch's RNG stream), and the running sum of log-softmax(processed row)[chosen] that
 //    _retrieve_avg_logprobs computes (scores * T undoes the temperature warper).  T and the
 //    seed live in a device control word, so one captured decode graph serves every fallback
-//    temperature.
+//    temperature.  tw_select_sample[_ts]_lp (the LP instantiations) also store that log-prob at the token's
+//    column of a per-token matrix (generate(return_token_logprobs=True)); tw_spec_accept_lp does so for the
+//    accepted columns of an assisted round.
 //  * tw_token_logprob: log-softmax of a raw logits row at one id (WhisperNoSpeechDetection).
 #include "common.h"
 #include "decode_impl.h"
@@ -149,6 +151,7 @@ struct AccP {
   int* last_ts; int* last_ts_a; int begin_col, ts_begin;
   float* slots; float* sum_logp;
   int* hist; int hist_cap;
+  float* tok_logp;            // nullable: the row of the per-token log-prob matrix (tw_spec_accept_lp)
 };
 __global__ __launch_bounds__(64) void spec_accept_kernel(AccP a) {
   const int lane = threadIdx.x;
@@ -185,8 +188,11 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(AccP a) {
       }
     }
   }
+  // column t + lane of the per-token matrix: the accepted slot, 0 at the columns rolled back
+  const float tlp = (a.tok_logp && lane >= 1 && lane <= adv) ? a.slots[lane - 1] : 0.f;
   __syncthreads();                                              // every read above precedes the stores below
   if (lane > adv && lane <= a.k + 1) a.ids[t + lane] = a.eos;   // columns past t + adv back to the eos fill
+  if (a.tok_logp && lane >= 1 && lane <= a.k + 1) a.tok_logp[t + lane] = tlp;
   if (a.slots && lane <= a.k) a.slots[lane] = 0.f;
   if (lane != 0) return;
   *a.t_dev = t + adv;
@@ -237,6 +243,8 @@ struct SelP {
   int begin_col;
   const uint32_t* ctl;        // nullable: per row b, ctl[3b] = bits of 1/T (0: greedy), ctl[3b+1], [3b+2] = seed lo, hi
   float* sum_logp;            // nullable: += log-prob of the chosen token while the row is live
+  float* tok_logp;            // nullable, read by the LP instantiations only: [b*ld_lp + col] = that log-prob (0 for a
+  int64_t ld_lp;              // row already finished)
   int vec;                    // rows 16-B aligned and padded to a multiple of 8 ids: 16-B loads
 };
 
@@ -320,6 +328,21 @@ __device__ __forceinline__ void block_lse(float& m, float& s, float (*sv)[4], in
 
 __device__ __forceinline__ bool bit(const uint32_t* m, int v) { return m && ((m[v >> 5] >> (v & 31)) & 1u); }
 
+// LP: the instantiations behind tw_select_sample[_ts]_lp, which also keep the step's log-prob per column (tok_logp).
+// Whether the scan gathers the row's logsumexp, and the owner thread's bookkeeping of the chosen token's log-prob
+// (lp() computes it): the value added to the running sum while the row is live is the value stored at the column.
+template <bool LP>
+__device__ __forceinline__ bool sel_lse(const SelP& p) {
+  return p.sum_logp != nullptr || (LP && p.tok_logp != nullptr);
+}
+template <bool LP, class F>
+__device__ __forceinline__ void sel_logp(const SelP& p, int b, bool fin, F&& lp) {
+  if (LP ? !sel_lse<true>(p) : (!p.sum_logp || fin)) return;
+  const float x = fin ? 0.f : lp();
+  if (p.sum_logp && !fin) p.sum_logp[b] += x;
+  if (LP && p.tok_logp) p.tok_logp[b * p.ld_lp + p.col] = x;
+}
+
 // Selection over a row is split into scan (per-thread accumulation over a slice of the vocabulary),
 // block reduction, and finish (thread 0: merge, pick, bookkeeping).  Few rows (batch-1 long-form): the
 // row is cut into G slices, one workgroup each, partials to the per-device scratch block, and a second
@@ -341,10 +364,10 @@ __device__ __forceinline__ void greedy_merge(GreedyAcc& a, const GreedyAcc& o, b
   if (sample && (o.sbest > a.sbest || (o.sbest == a.sbest && o.sbesti < a.sbesti))) { a.sbest = o.sbest; a.sbesti = o.sbesti; }
   if (lse) lse_merge(a.m, a.se, o.m, o.se);
 }
-template <typename E>
+template <bool LP, typename E>
 __device__ __forceinline__ void greedy_scan(const SelP& p, const E* row, int b, bool sample, float inv_t, uint64_t seed,
                                             GreedyAcc& a, int lo, int hi) {
-  const bool lse = p.sum_logp != nullptr;
+  const bool lse = sel_lse<LP>(p);
   for_row(p, row, [&](int v, float x, bool sup, bool beg) {
     if (sup || (p.apply_begin && beg)) x = -INFINITY;
     if (x > a.best || (x == a.best && v < a.besti)) { a.best = x; a.besti = v; }
@@ -363,7 +386,7 @@ __device__ __forceinline__ void greedy_block(GreedyAcc& a, bool sample, bool lse
   if (sample) block_argmax(a.sbest, a.sbesti, sv, si, 1);
   if (lse) block_lse(a.m, a.se, sv, 2);
 }
-template <typename E>
+template <bool LP, typename E>
 __device__ __forceinline__ void greedy_finish(const SelP& p, const E* row, int b, const GreedyAcc& a, bool sample) {
   int pick = sample ? a.sbesti : a.besti;
   if (pick == 0x7fffffff) pick = 0;              // every logit masked / NaN: id 0 (torch argmax of all -inf)
@@ -372,7 +395,7 @@ __device__ __forceinline__ void greedy_finish(const SelP& p, const E* row, int b
   p.ids[b * p.ld_ids + p.col] = tok;
   p.next[b] = tok;
   p.done[b] = (fin || tok == p.eos) ? 1 : 0;
-  if (p.sum_logp && !fin) p.sum_logp[b] += to_f32(row[pick]) - lse_val(a.m, a.se);
+  sel_logp<LP>(p, b, fin, [&] { return to_f32(row[pick]) - lse_val(a.m, a.se); });
 }
 __device__ __forceinline__ void sel_prologue(SelP& p) {
   if (p.t_dev) {
@@ -382,7 +405,7 @@ __device__ __forceinline__ void sel_prologue(SelP& p) {
 }
 
 // grid (G, B): G == 1 -> scan the whole row and finish; G > 1 -> partial of slice blockIdx.x into ws
-template <typename E>
+template <typename E, bool LP>
 __global__ __launch_bounds__(256) void greedy_select_kernel(SelP p, int slice, float* ws) {
   __shared__ float sv[4][4];
   __shared__ int si[4][4];
@@ -391,16 +414,16 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(SelP p, int slice, f
   float inv_t;
   uint64_t seed;
   read_ctl(p.ctl, b, inv_t, seed);
-  const bool sample = inv_t > 0.f, lse = p.sum_logp != nullptr;
+  const bool sample = inv_t > 0.f, lse = sel_lse<LP>(p);
   const E* row = (const E*)p.logits + b * p.ld;
   GreedyAcc a;
   greedy_init(a);
   const int lo = G == 1 ? 0 : g * slice, hi = G == 1 ? p.V : min(p.V, lo + slice);
-  greedy_scan(p, row, b, sample, inv_t, seed, a, lo, hi);
+  greedy_scan<LP>(p, row, b, sample, inv_t, seed, a, lo, hi);
   greedy_block(a, sample, lse, sv, si);
   if (tid != 0) return;
   if (G == 1) {
-    greedy_finish(p, row, b, a, sample);
+    greedy_finish<LP>(p, row, b, a, sample);
   } else {
     float* w = ws + ((int64_t)b * G + g) * SEL_WORDS;
     w[0] = a.best; w[1] = a.sbest; w[2] = a.m; w[3] = a.se;
@@ -408,7 +431,7 @@ __global__ __launch_bounds__(256) void greedy_select_kernel(SelP p, int slice, f
   }
 }
 
-template <typename E>
+template <typename E, bool LP>
 __global__ __launch_bounds__(64) void greedy_merge_kernel(SelP p, int G, const float* ws) {
   const int b = blockIdx.x;
   if (threadIdx.x != 0) return;
@@ -416,7 +439,7 @@ __global__ __launch_bounds__(64) void greedy_merge_kernel(SelP p, int G, const f
   float inv_t;
   uint64_t seed;
   read_ctl(p.ctl, b, inv_t, seed);
-  const bool sample = inv_t > 0.f, lse = p.sum_logp != nullptr;
+  const bool sample = inv_t > 0.f, lse = sel_lse<LP>(p);
   GreedyAcc a;
   greedy_init(a);
   for (int g = 0; g < G; ++g) {
@@ -426,7 +449,7 @@ __global__ __launch_bounds__(64) void greedy_merge_kernel(SelP p, int G, const f
     o.besti = __float_as_int(w[4]); o.sbesti = __float_as_int(w[5]);
     greedy_merge(a, o, sample, lse);
   }
-  greedy_finish(p, (const E*)p.logits + b * p.ld, b, a, sample);
+  greedy_finish<LP>(p, (const E*)p.logits + b * p.ld, b, a, sample);
 }
 
 
@@ -492,9 +515,9 @@ __device__ __forceinline__ bool ts_masked(const SelTsP& q, const TsRow& r, int v
   }
   return m;
 }
-template <typename E>
+template <bool LP, typename E>
 __device__ __forceinline__ void ts_scan(const SelTsP& q, const TsRow& r, const E* row, TsAcc& a, int lo, int hi) {
-  const bool lse = q.s.sum_logp != nullptr;
+  const bool lse = sel_lse<LP>(q.s);
   for_row(q.s, row, [&](int v, float x, bool sup, bool beg) {
     if (ts_masked(q, r, v, sup, beg) || !(x > -INFINITY)) return;
     if (v >= q.ts_begin) {
@@ -532,7 +555,7 @@ __device__ __forceinline__ void ts_block(TsAcc& a, bool lse, float (*sv)[8], int
 }
 // finish (whole workgroup; the merged accumulator in thread 0's a): the timestamp-mass rule, the
 // temperature-sampling pass over the processed row (Gumbel-max) when T > 0, the pick and bookkeeping
-template <typename E>
+template <typename E, bool LP>
 __device__ __forceinline__ void ts_finish(const SelTsP& q, const TsRow& r, int b, TsAcc& a, float (*sx)[4],
                                           int (*sxi)[4]) {
   __shared__ int s_mask_text;
@@ -573,20 +596,20 @@ __device__ __forceinline__ void ts_finish(const SelTsP& q, const TsRow& r, int b
     p.next[b] = tok;
     p.done[b] = (fin || tok == p.eos) ? 1 : 0;
     if (!fin && tok >= q.ts_begin) q.last_ts[b] = (int)tok;
-    if (p.sum_logp && !fin) {
+    sel_logp<LP>(p, b, fin, [&] {
       float lse = ts_l;
       if (!mask_text) {
         float m = a.tm, ss = a.tse;
         if (a.bs > -INFINITY) lse_merge(m, ss, a.bs, a.se);
         lse = lse_val(m, ss);
       }
-      p.sum_logp[b] += to_f32(row[best]) - lse;
-    }
+      return to_f32(row[best]) - lse;
+    });
   }
 }
 
 // grid (G, B): G == 1 -> whole row + finish; G > 1 -> partial of slice blockIdx.x into ws
-template <typename E>
+template <typename E, bool LP>
 __global__ __launch_bounds__(256) void greedy_select_ts_kernel(SelTsP q, int slice, float* ws) {
   __shared__ float sv[4][8];
   __shared__ int si[4][2];
@@ -595,15 +618,15 @@ __global__ __launch_bounds__(256) void greedy_select_ts_kernel(SelTsP q, int sli
   const int g = blockIdx.x, G = gridDim.x, b = blockIdx.y;
   if (q.s.t_dev) q.s.col += *q.s.t_dev;
   const TsRow r = ts_row(q, b);
-  const bool lse = q.s.sum_logp != nullptr;
+  const bool lse = sel_lse<LP>(q.s);
   const E* row = (const E*)q.s.logits + b * q.s.ld;
   TsAcc a;
   ts_init(a);
   const int lo = G == 1 ? 0 : g * slice, hi = G == 1 ? q.s.V : min(q.s.V, lo + slice);
-  ts_scan(q, r, row, a, lo, hi);
+  ts_scan<LP>(q, r, row, a, lo, hi);
   ts_block(a, lse, sv, si);
   if (G == 1) {
-    ts_finish<E>(q, r, b, a, sx, sxi);
+    ts_finish<E, LP>(q, r, b, a, sx, sxi);
   } else if (threadIdx.x == 0) {
     float* w = ws + ((int64_t)b * G + g) * SEL_WORDS;
     w[0] = a.bt; w[1] = a.bs; w[2] = a.se; w[3] = a.tm; w[4] = a.tse;
@@ -611,14 +634,14 @@ __global__ __launch_bounds__(256) void greedy_select_ts_kernel(SelTsP q, int sli
   }
 }
 
-template <typename E>
+template <typename E, bool LP>
 __global__ __launch_bounds__(256) void ts_merge_kernel(SelTsP q, int G, const float* ws) {
   __shared__ float sx[4][4];
   __shared__ int sxi[4][4];
   const int b = blockIdx.x;
   if (q.s.t_dev) q.s.col += *q.s.t_dev;
   const TsRow r = ts_row(q, b);
-  const bool lse = q.s.sum_logp != nullptr;
+  const bool lse = sel_lse<LP>(q.s);
   TsAcc a;
   ts_init(a);
   if (threadIdx.x == 0)
@@ -629,7 +652,7 @@ __global__ __launch_bounds__(256) void ts_merge_kernel(SelTsP q, int G, const fl
       o.it = __float_as_int(w[5]); o.is = __float_as_int(w[6]);
       ts_merge(a, o, lse);
     }
-  ts_finish<E>(q, r, b, a, sx, sxi);
+  ts_finish<E, LP>(q, r, b, a, sx, sxi);
 }
 
 // out[b] = log_softmax(logits[b, :V])[token]   (fp32 of the bf16 / fp32 row)
@@ -717,15 +740,18 @@ int sel_slices(int B, int V) {
   return (V + slice - 1) / slice;
 }
 
-// the scan and merge kernels of the two selection families (plain / timestamp rules) and the merge's block size
+// the scan and merge kernels of the two selection families (plain / timestamp rules) and the merge's block size;
+// LP: the instantiations that also store the per-token log-prob (the _lp entries with a tok_logp)
+template <bool LP>
 struct GreedyK {
-  template <typename E> static constexpr auto scan = greedy_select_kernel<E>;
-  template <typename E> static constexpr auto merge = greedy_merge_kernel<E>;
+  template <typename E> static constexpr auto scan = greedy_select_kernel<E, LP>;
+  template <typename E> static constexpr auto merge = greedy_merge_kernel<E, LP>;
   static constexpr int merge_block = 64;
 };
+template <bool LP>
 struct TsK {
-  template <typename E> static constexpr auto scan = greedy_select_ts_kernel<E>;
-  template <typename E> static constexpr auto merge = ts_merge_kernel<E>;
+  template <typename E> static constexpr auto scan = greedy_select_ts_kernel<E, LP>;
+  template <typename E> static constexpr auto merge = ts_merge_kernel<E, LP>;
   static constexpr int merge_block = 256;
 };
 template <class K, class P>
@@ -755,8 +781,12 @@ SelP sel_fill(const void* logits, int64_t ld, int V, const uint32_t* suppress_bi
   p.suppress = suppress_bits; p.begin = begin_bits; p.apply_begin = apply_begin;
   p.eos = eos; p.done = done; p.ids = ids; p.ld_ids = ld_ids; p.col = col; p.next = next_ids;
   p.t_dev = t_dev; p.begin_col = begin_col;
-  p.ctl = ctl; p.sum_logp = sum_logp; p.vec = sel_vec(logits, ld, V);
+  p.ctl = ctl; p.sum_logp = sum_logp; p.tok_logp = nullptr; p.ld_lp = 0; p.vec = sel_vec(logits, ld, V);
   return p;
+}
+// the checks the _lp entries add: something to track, and a row stride that holds the column when the host knows it
+bool lp_bad(const float* sum_logp, const float* tok_logp, int64_t ld_lp, int col, const int* t_dev) {
+  return (!sum_logp && !tok_logp) || (tok_logp && (ld_lp < 1 || col < 0 || (!t_dev && ld_lp <= col)));
 }
 
 // (dec_fill and dec_split: decode_impl.h)
@@ -818,18 +848,33 @@ int launch_mq(const DecP& p, const MqP& q, int B, int nchunk, bool split, int dt
 }  // namespace
 
 namespace {
-// tw_greedy_select_ts (ctl, sum_logp null) and tw_select_sample_ts
+// tw_greedy_select_ts (ctl, sum_logp null), tw_select_sample_ts (tok_logp null) and tw_select_sample_ts_lp
 int select_ts(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
               const uint32_t* begin_bits, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids,
               int col, int64_t* next_ids, const int* t_dev, int begin_col, int ts_begin,
               int no_ts, int max_initial, int* last_ts, const uint32_t* ctl,
-              float* sum_logp, hipStream_t stream) {
+              float* sum_logp, float* tok_logp, int64_t ld_lp, hipStream_t stream) {
   if (sel_bad(ld, V, done, ids, next_ids) || !last_ts || ts_begin <= eos || ts_begin > V) return TW_EINVAL;
   SelTsP q;
   q.s = sel_fill(logits, ld, V, suppress_bits, begin_bits, 0, eos, done, ids, ld_ids, col, next_ids, t_dev, begin_col,
                  ctl, sum_logp);
   q.begin_col = begin_col; q.ts_begin = ts_begin; q.no_ts = no_ts; q.max_initial = max_initial; q.last_ts = last_ts;
-  return launch_select<TsK>(q, B, V, logits_dtype, stream);
+  if (!tok_logp) return launch_select<TsK<false>>(q, B, V, logits_dtype, stream);
+  q.s.tok_logp = tok_logp; q.s.ld_lp = ld_lp;
+  return launch_select<TsK<true>>(q, B, V, logits_dtype, stream);
+}
+// tw_select_sample (tok_logp null) and tw_select_sample_lp
+int select_plain(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
+                 const uint32_t* begin_bits, int apply_begin, int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids,
+                 int col, int64_t* next_ids, const int* t_dev, int begin_col, const uint32_t* ctl, float* sum_logp,
+                 float* tok_logp, int64_t ld_lp, hipStream_t stream) {
+  if (sel_bad(ld, V, done, ids, next_ids)) return TW_EINVAL;
+  if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
+  SelP p = sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids, col, next_ids, t_dev,
+                    begin_col, ctl, sum_logp);
+  if (!tok_logp) return launch_select<GreedyK<false>>(p, B, V, logits_dtype, stream);
+  p.tok_logp = tok_logp; p.ld_lp = ld_lp;
+  return launch_select<GreedyK<true>>(p, B, V, logits_dtype, stream);
 }
 }  // namespace
 
@@ -839,7 +884,7 @@ extern "C" int tw_greedy_select_ts(const void* logits, int64_t ld, int logits_dt
                                    int no_ts, int max_initial, int* last_ts, hipStream_t stream) {
   if (B <= 0) return TW_OK;
   return select_ts(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, eos, done, ids, ld_ids, col, next_ids,
-                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, nullptr, nullptr, stream);
+                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, nullptr, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
@@ -850,7 +895,20 @@ extern "C" int tw_select_sample_ts(const void* logits, int64_t ld, int logits_dt
   if (B <= 0) return TW_OK;
   if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
   return select_ts(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, eos, done, ids, ld_ids, col, next_ids,
-                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, ctl, sum_logp, stream);
+                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, ctl, sum_logp, nullptr, 0, stream);
+}
+
+extern "C" int tw_select_sample_ts_lp(const void* logits, int64_t ld, int logits_dtype, int B, int V,
+                                      const uint32_t* suppress_bits, const uint32_t* begin_bits, int64_t eos,
+                                      uint8_t* done, int64_t* ids, int64_t ld_ids, int col, int64_t* next_ids,
+                                      const int* t_dev, int begin_col, int ts_begin, int no_ts, int max_initial,
+                                      int* last_ts, const uint32_t* ctl, float* sum_logp, float* tok_logp,
+                                      int64_t ld_lp, hipStream_t stream) {
+  if (B <= 0) return TW_OK;
+  if (lp_bad(sum_logp, tok_logp, ld_lp, col, t_dev)) return TW_EINVAL;
+  if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
+  return select_ts(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, eos, done, ids, ld_ids, col, next_ids,
+                   t_dev, begin_col, ts_begin, no_ts, max_initial, last_ts, ctl, sum_logp, tok_logp, ld_lp, stream);
 }
 
 extern "C" int tw_token_logprob(const void* logits, int64_t ld, int logits_dtype, int B, int V, int token,
@@ -995,22 +1053,31 @@ extern "C" int tw_decode_attn_mq(const void* q, int64_t sqb, int64_t sqq, const 
   }
 }
 
-extern "C" int tw_spec_accept(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev,
-                              int* t_dev_a, int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a,
-                              uint8_t* done_snap, int* last_ts, int* last_ts_a, int begin_col, int ts_begin,
-                              float* slots, float* sum_logp, int* hist, int hist_cap, hipStream_t stream) {
+extern "C" int tw_spec_accept_lp(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev,
+                                 int* t_dev_a, int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a,
+                                 uint8_t* done_snap, int* last_ts, int* last_ts_a, int begin_col, int ts_begin,
+                                 float* slots, float* sum_logp, float* tok_logp, int* hist, int hist_cap,
+                                 hipStream_t stream) {
   if (k < 1 || k >= DA_MQ || !drafts || !ids || !t_dev || !cur || !done || !done_snap || t_cap < 1 || begin_col < 0)
     return TW_EINVAL;
-  if ((sum_logp != nullptr) != (slots != nullptr) || (hist && hist_cap < 1)) return TW_EINVAL;
+  if ((sum_logp != nullptr) != (slots != nullptr) || (hist && hist_cap < 1) || (tok_logp && !slots)) return TW_EINVAL;
   AccP a;
   a.drafts = drafts; a.k = k; a.ids = ids; a.t_cap = t_cap; a.eos = eos;
   a.t_dev = t_dev; a.t_dev_a = t_dev_a; a.cur = cur; a.cur_a = cur_a;
   a.done = done; a.done_a = done_a; a.done_snap = done_snap;
   a.last_ts = last_ts; a.last_ts_a = last_ts_a; a.begin_col = begin_col; a.ts_begin = ts_begin;
-  a.slots = slots; a.sum_logp = sum_logp; a.hist = hist; a.hist_cap = hist_cap;
+  a.slots = slots; a.sum_logp = sum_logp; a.hist = hist; a.hist_cap = hist_cap; a.tok_logp = tok_logp;
   hipLaunchKernelGGL(spec_accept_kernel, dim3(1), dim3(64), 0, stream, a);
   TW_CHECK_LAUNCH();
   return TW_OK;
+}
+
+extern "C" int tw_spec_accept(const int64_t* drafts, int k, int64_t* ids, int t_cap, int64_t eos, int* t_dev,
+                              int* t_dev_a, int64_t* cur, int64_t* cur_a, uint8_t* done, uint8_t* done_a,
+                              uint8_t* done_snap, int* last_ts, int* last_ts_a, int begin_col, int ts_begin,
+                              float* slots, float* sum_logp, int* hist, int hist_cap, hipStream_t stream) {
+  return tw_spec_accept_lp(drafts, k, ids, t_cap, eos, t_dev, t_dev_a, cur, cur_a, done, done_a, done_snap, last_ts,
+                           last_ts_a, begin_col, ts_begin, slots, sum_logp, nullptr, hist, hist_cap, stream);
 }
 
 extern "C" int tw_embed_step_multi(const int64_t* ids, const void* tok, int tok_dtype, const void* pos, int pos_dtype,
@@ -1030,9 +1097,9 @@ extern "C" int tw_greedy_select(const void* logits, int64_t ld, int logits_dtype
                                 hipStream_t stream) {
   if (B <= 0) return TW_OK;
   if (sel_bad(ld, V, done, ids, next_ids)) return TW_EINVAL;
-  return launch_select<GreedyK>(sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids,
-                                         col, next_ids, t_dev, begin_col, nullptr, nullptr),
-                                B, V, logits_dtype, stream);
+  return launch_select<GreedyK<false>>(sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids,
+                                                ld_ids, col, next_ids, t_dev, begin_col, nullptr, nullptr),
+                                       B, V, logits_dtype, stream);
 }
 
 extern "C" int tw_select_sample(const void* logits, int64_t ld, int logits_dtype, int B, int V, const uint32_t* suppress_bits,
@@ -1040,9 +1107,17 @@ extern "C" int tw_select_sample(const void* logits, int64_t ld, int logits_dtype
                                 int64_t ld_ids, int col, int64_t* next_ids, const int* t_dev, int begin_col,
                                 const uint32_t* ctl, float* sum_logp, hipStream_t stream) {
   if (B <= 0) return TW_OK;
-  if (sel_bad(ld, V, done, ids, next_ids)) return TW_EINVAL;
-  if (B >= (1 << 21) || V >= (1 << 21)) return TW_EUNSUPPORTED;     // RNG key widths
-  return launch_select<GreedyK>(sel_fill(logits, ld, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids,
-                                         col, next_ids, t_dev, begin_col, ctl, sum_logp),
-                                B, V, logits_dtype, stream);
+  return select_plain(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids, col,
+                      next_ids, t_dev, begin_col, ctl, sum_logp, nullptr, 0, stream);
+}
+
+extern "C" int tw_select_sample_lp(const void* logits, int64_t ld, int logits_dtype, int B, int V,
+                                   const uint32_t* suppress_bits, const uint32_t* begin_bits, int apply_begin,
+                                   int64_t eos, uint8_t* done, int64_t* ids, int64_t ld_ids, int col, int64_t* next_ids,
+                                   const int* t_dev, int begin_col, const uint32_t* ctl, float* sum_logp,
+                                   float* tok_logp, int64_t ld_lp, hipStream_t stream) {
+  if (B <= 0) return TW_OK;
+  if (lp_bad(sum_logp, tok_logp, ld_lp, col, t_dev)) return TW_EINVAL;
+  return select_plain(logits, ld, logits_dtype, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, ld_ids, col,
+                      next_ids, t_dev, begin_col, ctl, sum_logp, tok_logp, ld_lp, stream);
 }

@@ -5,8 +5,10 @@ synthetic 30 s features; eos is suppressed so every clip runs exactly --new-toke
     python tools/bench_decode.py [--batch 64] [--new-tokens 224] [--clips 128] [--eager] [--dtype float16]
                                  [--repetition_penalty 1.3] [--no_repeat_ngram_size 3]
                                  [--language zh | auto | zh,en,...] [--runs 5] [--detect]
+                                 [--return_token_logprobs]
 --language auto detects every clip's language (generate(language="auto")); a comma list names one language per clip
 (repeated to the batch).  --runs N times N calls and prints each; --detect times detect_language alone instead.
+--return_token_logprobs decodes with generate(return_token_logprobs=True) (the tracking selectors' _lp entries).
 """
 import argparse
 import os
@@ -30,6 +32,8 @@ def main():
     ap.add_argument("--language", default="zh", help="a language, 'auto', or a comma list (one per clip, cycled)")
     ap.add_argument("--runs", type=int, default=0, help="time this many single calls and print each (ms)")
     ap.add_argument("--detect", action="store_true", help="time detect_language alone (with --runs)")
+    ap.add_argument("--return_token_logprobs", action="store_true",
+                    help="generate(return_token_logprobs=True): per-token log-probs beside the ids")
     ap.add_argument("--longform-seconds", type=float, default=0.0,
                     help="config c5: one input of this many seconds, return_timestamps, --new-tokens per window")
     a = ap.parse_args()
@@ -69,6 +73,8 @@ def main():
               f"{dt / max(steps, 1) * 1e3:.2f} ms/step at batch 1)", flush=True)
         return
     rep = dict(repetition_penalty=a.repetition_penalty, no_repeat_ngram_size=a.no_repeat_ngram_size)
+    if a.return_token_logprobs:
+        rep["return_token_logprobs"] = True
     feats = torch.randn(a.batch, 80, 3000, device="cuda") * 0.3
     m.generate(feats[:2], language=lang(2), task="transcribe", max_new_tokens=4, use_graph=not a.eager, **rep)  # warm-up
     torch.cuda.synchronize()
@@ -86,7 +92,8 @@ def main():
             one()
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
-        what = "detect_language" if a.detect else f"generate language={a.language} {a.new_tokens} tokens"
+        what = "detect_language" if a.detect else (f"generate language={a.language} {a.new_tokens} tokens"
+                                                   f"{' token_logprobs' if a.return_token_logprobs else ''}")
         per = "" if a.detect else f", median {sorted(ms)[len(ms) // 2] / a.new_tokens:.3f} ms/step"
         print(f"{what} {a.config} {a.dtype} batch {a.batch}: per call ms {' '.join(f'{x:.2f}' for x in ms)} "
               f"(min {min(ms):.2f}, median {sorted(ms)[len(ms) // 2]:.2f}, max {max(ms):.2f}{per})", flush=True)
@@ -96,10 +103,12 @@ def main():
     for _ in range(n_sub):
         out = m.generate(feats, language=lang(a.batch), task="transcribe", max_new_tokens=a.new_tokens,
                          use_graph=not a.eager, **rep)
+        out = out[0] if a.return_token_logprobs else out
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     clips = n_sub * a.batch
-    print(f"c4 greedy {a.config} {a.dtype} penalty {a.repetition_penalty} ngram {a.no_repeat_ngram_size}: "
+    print(f"c4 greedy {a.config} {a.dtype} penalty {a.repetition_penalty} ngram {a.no_repeat_ngram_size}"
+          f"{' token_logprobs' if a.return_token_logprobs else ''}: "
           f"{clips} clips x {out.shape[1]} tokens, batch {a.batch}: {dt:.2f} s "
           f"-> {clips / dt:.2f} clips/s, {dt / n_sub / a.new_tokens * 1e3:.2f} ms/step "
           f"({'eager' if a.eager else 'graph'})", flush=True)

@@ -81,6 +81,12 @@ SIGNATURES = {
     "tw_greedy_select_ts": [P, I64, I32, I32, I32, P, P, I64, P, P, I64, I32, P, P, I32, I32, I32, I32, P, P],
     "tw_select_sample": [P, I64, I32, I32, I32, P, P, I32, I64, P, P, I64, I32, P, P, I32, P, P, P],
     "tw_select_sample_ts": [P, I64, I32, I32, I32, P, P, I64, P, P, I64, I32, P, P, I32, I32, I32, I32, P, P, P, P],
+    # per-token log-probs (generate(return_token_logprobs=True)): the tracking selectors and the acceptance kernel
+    # with a [B][ld_lp] fp32 matrix / its row
+    "tw_select_sample_lp": [P, I64, I32, I32, I32, P, P, I32, I64, P, P, I64, I32, P, P, I32, P, P, P, I64, P],
+    "tw_select_sample_ts_lp": [P, I64, I32, I32, I32, P, P, I64, P, P, I64, I32, P, P, I32, I32, I32, I32, P, P, P, P,
+                               I64, P],
+    "tw_spec_accept_lp": [P, I32, P, I32, I64, P, P, P, P, P, P, P, P, P, I32, I32, P, P, P, P, I32, P],
     "tw_token_logprob": [P, I64, I32, I32, I32, I32, P, P],
     "tw_repeat_process": [P, I64, I32, I32, I32, P, I64, I32, P, F32, I32, P, I64, P],
     "tw_lang_detect": [P, I64, I32, I32, I32, P, I32, P, I64, P, I64, P],

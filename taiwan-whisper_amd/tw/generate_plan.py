@@ -210,6 +210,7 @@ class Request:
     track: bool                     # the selection tracks log-probs / samples (a threshold or a temperature needs it)
     trace: list                     # the tests' private hooks _trace and _keep
     keep: list
+    return_token_logprobs: bool = False     # the log-prob of every returned token beside the ids (forces track)
 
     @property
     def detected(self):
@@ -220,9 +221,9 @@ class Request:
 def plan_generate(cfg, gc, *, rows, frames, have_features, have_encoder_outputs, max_length=None, num_beams=1,
                   return_timestamps=False, language=None, task=None, decoder_input_ids=None, max_new_tokens=None,
                   use_graph=None, prompt_ids=None, prompt_condition_type=None, assistant_model=None,
-                  num_assistant_tokens=None, return_language=False, **kw) -> Request:
+                  num_assistant_tokens=None, return_language=False, return_token_logprobs=False, **kw) -> Request:
     """generate's arguments -> the Request, or the argument error generate raises; the checks in the order of their
-    precedence.  cfg, gc: the model's config and its resolved generation config.  rows: the batch size of the inputs
+    precedence.  return_token_logprobs reaches here through generate's **kw: the planner owns the keyword.  cfg, gc: the model's config and its resolved generation config.  rows: the batch size of the inputs
     (0 without any); frames: input_features.shape[-1] or None."""
     unknown = sorted(set(kw) - GENERATE_KEYWORDS)
     if unknown:
@@ -249,15 +250,16 @@ def plan_generate(cfg, gc, *, rows, frames, have_features, have_encoder_outputs,
     thresholds = [kw.get(n) for n in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold")]
     seed = int(kw.get("seed", 0))
     penalty, ngram = repeat_options(gc, kw)
-    if penalty != 1.0 or ngram > 0:
-        # HF's beam search applies the two processors to log-probabilities, and the verify pass of assisted decoding
-        # would need a history per query row: neither is built
-        if nb > 1:
-            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with beam search (num_beams > 1) "
-                                      "is not implemented")
-        if assist is not None:
-            raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with assisted decoding "
-                                      "(assistant_model) is not implemented")
+    # HF's beam search applies the two repeat processors to log-probabilities, and it scores its hypotheses in torch:
+    # their per-token values are not kept.  The verify pass of assisted decoding would need a history per query row
+    # for the repeat processors.  None of these is built
+    beamless = " and ".join(n for n in (_repeat_names(penalty, ngram),
+                                        "return_token_logprobs" if return_token_logprobs else "") if n)
+    if nb > 1 and beamless:
+        raise NotImplementedError(f"tw generate: {beamless} with beam search (num_beams > 1) is not implemented")
+    if assist is not None and (penalty != 1.0 or ngram > 0):
+        raise NotImplementedError(f"tw generate: {_repeat_names(penalty, ngram)} with assisted decoding "
+                                  "(assistant_model) is not implemented")
     # a list and "auto" are resolved here; a single language after the other checks, where its error has always
     # come (with decoder_input_ids the caller owns the prompt and a single `language` is not looked at)
     per_row = isinstance(language, (list, tuple)) or (isinstance(language, str) and language == AUTO)
@@ -305,5 +307,5 @@ def plan_generate(cfg, gc, *, rows, frames, have_features, have_encoder_outputs,
         condition_on_prev_tokens=bool(kw.get("condition_on_prev_tokens") or False), seed=seed,
         fallback_batch=bool(kw.get("fallback_batch", True)),
         track=(thresholds[1] is not None or thresholds[2] is not None or any(t and t > 0 for t in temps)
-               or len(temps) > 1),
-        trace=kw.get("_trace"), keep=kw.get("_keep"))
+               or len(temps) > 1 or bool(return_token_logprobs)),
+        trace=kw.get("_trace"), keep=kw.get("_keep"), return_token_logprobs=bool(return_token_logprobs))

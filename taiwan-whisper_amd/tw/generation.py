@@ -402,7 +402,8 @@ class _Select:
     SuppressTokensAtBegin and, with timestamps, WhisperTimeStampLogitsProcessor + argmax."""
 
     def __init__(self, gc, B, V, T_max, P, dev, timestamps, track=False, repetition_penalty=1.0,
-                 no_repeat_ngram_size=0, Vp=None):
+                 no_repeat_ngram_size=0, Vp=None, logp=False):
+        track = track or logp            # the per-token values come from the tracking kernels (1/T = 0: argmax)
         self.V, self.P, self.ts, self.track = V, P, timestamps, track
         # HF RepetitionPenaltyLogitsProcessor / NoRepeatNGramLogitsProcessor: launch-time scalars of the pre-pass
         # (baked into a captured step) and its fp32 output rows [B][Vp]; neither active: no scratch, today's calls
@@ -424,6 +425,9 @@ class _Select:
         self.B = B
         self.ctl = torch.zeros(3 * B, dtype=torch.int32, device=dev) if track else None
         self.sum_logp = torch.zeros(B, dtype=torch.float32, device=dev) if track else None
+        # logp (generate(return_token_logprobs=True)): the log-prob of every selected token at its column of the id
+        # matrix, written by the _lp kernels (baked into a captured step); off: nothing allocated, today's calls
+        self.tok_logp = torch.zeros(B, T_max, dtype=torch.float32, device=dev) if logp else None
 
     def reset(self, prompt, temperature=0.0, seed=0):
         """temperature / seed: one value for every row, or one per row."""
@@ -433,6 +437,8 @@ class _Select:
         self.last_ts.fill_(-1)
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * self.B
         seeds = list(seed) if isinstance(seed, (list, tuple)) else [seed] * self.B
+        if self.tok_logp is not None:
+            self.tok_logp.zero_()
         if self.track:
             self.sum_logp.zero_()
             F.sample_ctl(temps, seeds, self.ctl)
@@ -445,7 +451,9 @@ class _Select:
     def launch(self, logits, t_dev, next_ids, col=1, sum_logp=None, B=1):
         """The selection kernel this selector's mode takes (plain, timestamps, or the tracking forms with their
         per-row control word) on `logits` ([B][Vp] rows) into ids[:, *t_dev + col] and next_ids.  sum_logp: where the
-        tracking forms accumulate (default: the selector's running sum).  With a repetition penalty or a no-repeat
+        tracking forms accumulate (default: the selector's running sum, and with it the selector's per-token matrix
+        when it keeps one; a caller that redirects the sum -- the verify pass's slots -- stores the per-token values
+        itself, tw_spec_accept_lp).  With a repetition penalty or a no-repeat
         n-gram size, tw_repeat_process first writes the rows, processed for the history ids[:, :*t_dev + col], to the
         selector's fp32 scratch, and the selection kernel reads that instead (HF runs the two processors first)."""
         Vp = logits.stride(0)
@@ -455,13 +463,14 @@ class _Select:
                                       self.ngram, t_dev=t_dev)
         if self.track:
             slp = self.sum_logp if sum_logp is None else sum_logp
+            lp = dict(tok_logp=self.tok_logp) if sum_logp is None and self.tok_logp is not None else {}
             if self.ts:
                 F.select_sample_ts(logits, Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids,
                                    col, next_ids, self.last_ts, self.P, self.ctl, slp, ts_begin=self.no_ts + 1,
-                                   no_ts=self.no_ts, max_initial=self.max_initial, t_dev=t_dev)
+                                   no_ts=self.no_ts, max_initial=self.max_initial, t_dev=t_dev, **lp)
             else:
                 F.select_sample(logits, Vp, B, self.V, self.sup, self.beg, False, self.eos, self.done,
-                                self.ids, col, next_ids, self.ctl, slp, t_dev=t_dev, begin_col=self.P)
+                                self.ids, col, next_ids, self.ctl, slp, t_dev=t_dev, begin_col=self.P, **lp)
         elif self.ts:
             F.greedy_select_ts(logits, Vp, B, self.V, self.sup, self.beg, self.eos, self.done, self.ids, col,
                                next_ids, self.last_ts, self.P, ts_begin=self.no_ts + 1, no_ts=self.no_ts,
@@ -514,6 +523,8 @@ class _PromptedDecode:
         B = gen.shape[0]
         first = torch.where(is_eos.any(1), is_eos.int().argmax(1), torch.full((B,), gen.shape[1]))
         L = int(min(gen.shape[1], int(first.max()) + 1)) if B else 0
+        if self.sel.tok_logp is not None:       # the same columns of the per-token log-probs, beside the ids
+            return gen[:, :L], self.sel.tok_logp[:, self.P:self.P + L]
         return gen[:, :L]
 
 
@@ -522,17 +533,18 @@ class _Decoder(_PromptedDecode):
     the captured step graph stays valid because every buffer it touches is reused in place."""
 
     def __init__(self, model, gc, B, Tk, P, max_length, timestamps, use_graph, track=False, repetition_penalty=1.0,
-                 no_repeat_ngram_size=0):
+                 no_repeat_ngram_size=0, logp=False):
         self.m, self.P, self.T_max, self.use_graph = model, P, max_length, use_graph
         self.sess = None
         self.sel = _Select(gc, B, model.config.vocab_size, max_length, P, model.device, timestamps, track,
-                           repetition_penalty, no_repeat_ngram_size, Vp=model.Vp)
+                           repetition_penalty, no_repeat_ngram_size, Vp=model.Vp, logp=logp)
         self.B, self.Tk = B, Tk
         self.ns_logp = torch.zeros(B, dtype=torch.float32, device=model.device) if track else None
 
     def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False,
             detect=None):
-        """prompt: int64 [B, P] (device) -> generated ids [B, L] (device), HF trimming.
+        """prompt: int64 [B, P] (device) -> generated ids [B, L] (device), HF trimming; a decoder built with
+        logp=True -> (ids, per-token log-probs fp32 [B, L]: 0 after a row's eos).
         detect: the device table of language ids -> the languages are detected inside the prefill (_prefill) and
         sel.ids[:, 1] holds them afterwards; `prompt` carries any valid language id there.
         pads: per-row count of leading pad columns of `prompt` (rows left-padded to the longest prompt of the batch,
@@ -579,14 +591,16 @@ class _SpecDecoder(_PromptedDecode):
     run with it; tw_decode_attn_mq computes each query as the single-query kernel does), so the ids, the summed
     log-prob and the no-speech probability equal the plain decode's."""
 
-    def __init__(self, model, assistant, gc, Tk, P, max_length, timestamps, use_graph, track=False, k=None):
+    def __init__(self, model, assistant, gc, Tk, P, max_length, timestamps, use_graph, track=False, k=None,
+                 logp=False):
+        track = track or logp
         self.m, self.a, self.P, self.T_max, self.use_graph = model, assistant, P, max_length, use_graph
         self.k = DEFAULT_ASSISTANT_TOKENS if k is None else int(k)
         assert 1 <= self.k <= MAX_ASSISTANT_TOKENS
         Q = self.k + 1
         dev = model.device
         V = model.config.vocab_size
-        self.sel = _Select(gc, 1, V, max_length + Q, P, dev, timestamps, track)
+        self.sel = _Select(gc, 1, V, max_length + Q, P, dev, timestamps, track, logp=logp)
         self.sel_a = _Select(gc, 1, V, 1, P, dev, timestamps, False)     # the assistant: plain greedy, own flags
         self.sel_a.ids = self.sel.ids
         self.B, self.Tk = 1, Tk
@@ -615,7 +629,8 @@ class _SpecDecoder(_PromptedDecode):
         F.spec_accept(vin[1:], k, sel.ids[0], self.T_max, sel.eos, st.t_dev, vin[:1], sel.done, self.done_snap,
                       t_dev_a=sa.t_dev, done_a=sel_a.done, last_ts=sel.last_ts if sel.ts else None,
                       last_ts_a=sel_a.last_ts if sel.ts else None, begin_col=self.P, ts_begin=sel.no_ts + 1,
-                      slots=self.slots, sum_logp=sel.sum_logp if self.slots is not None else None, hist=self.hist)
+                      slots=self.slots, sum_logp=sel.sum_logp if self.slots is not None else None, hist=self.hist,
+                      tok_logp=sel.tok_logp[0] if sel.tok_logp is not None else None)
 
     def run(self, enc16, prompt, temperature=0.0, seed=0, no_speech=None, pads=None, shift_positions=False,
             enc_a=None):
@@ -886,6 +901,17 @@ def retrieve_segment(seq, seek_num_frames, ts_begin=50364, input_stride=2):
     return segs, off
 
 
+def segment_logprobs(lps, segs):
+    """The per-token values `lps` of a window's tokens cut as retrieve_segment cut the tokens into `segs`: the
+    segments are consecutive slices from the window's first token (tokens after the last cut belong to none)."""
+    out, last = [], 0
+    for sg in segs:
+        out.append(list(lps[last:last + len(sg)]))
+        last += len(sg)
+    assert last <= len(lps)
+    return out
+
+
 def _language_ids(model, gc, rq, chunks):
     """The request's languages as one id per row, or None (no language token): the named ids as they are; "auto" with
     a pass of its own (OWN_PASS) runs _detect on every (enc16, B, Tk) of `chunks` -- short-form: the call's encoder
@@ -940,7 +966,15 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
     the B ids back.  Beam search decodes one prompt, so rows of different languages raise NotImplementedError.
     return_language=True returns (ids, language ids int64 [B] on the device) for any language form but None (there is
     no language to return: ValueError).  With decoder_input_ids the caller owns the prompt: `language` is not looked
-    at, as before, and return_language raises ValueError."""
+    at, as before, and return_language raises ValueError.
+    return_token_logprobs=True (a keyword of the planner, through **kw): returns (ids, logprobs), or (ids, languages,
+    logprobs) with return_language.  logprobs: fp32 on the ids' device, the ids' shape; element [b, j] is the log-prob
+    of ids[b, j] under the log-softmax of the processed scores of its step -- after the repeat processors, the
+    suppress masks and the timestamp rules, at temperature 1 (HF's _retrieve_avg_logprobs convention: what
+    compute_transition_scores gives on the processed scores) -- as the selection kernel computed it, and 0.0 where the
+    engine selected nothing: after a row's eos and in the padding between rows.  Long-form: a token carries the
+    value of the attempt that was kept.  It forces the tracking selection kernels (argmax at 1/T = 0: the ids do not
+    change); with num_beams > 1 it raises NotImplementedError."""
     gc = _resolve_gc(model)
     hidden = _unwrap(encoder_outputs)
     given = hidden if hidden is not None else input_features
@@ -979,6 +1013,8 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
             lang_out = torch.tensor(langs, dtype=torch.int64, device=dev)
     P = prompt.shape[1]
     ml = total_length(cfg, gc, P, rq.max_length, rq.max_new_tokens)
+    want_lp = rq.return_token_logprobs
+    lpkw = dict(logp=True) if want_lp else {}        # off: the decoders are built and run as before
     if P >= ml:
         # nothing is decoded, so there is no prefill to detect in: the languages, when asked for, take their own pass
         if fused and rq.return_language:
@@ -988,7 +1024,7 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         if B != 1:
             raise ValueError("tw generate: assisted decoding takes a single input (batch size 1), as HF's does")
         enc_a = assistant_encoder(rq.assistant, model, enc16, input_features)
-        dec = _SpecDecoder(model, rq.assistant, gc, Tk, P, ml, rq.timestamps, rq.use_graph, k=rq.k)
+        dec = _SpecDecoder(model, rq.assistant, gc, Tk, P, ml, rq.timestamps, rq.use_graph, k=rq.k, **lpkw)
         if rq.keep is not None:
             rq.keep.append(dec)
         out = dec.run(enc16, prompt.to(dev), enc_a=enc_a)
@@ -1000,12 +1036,15 @@ def generate(model, input_features=None, max_length=None, num_beams=1, return_ti
         out = _BeamDecoder(model, gc, B, rq.num_beams, Tk, P, ml).run(enc16, prompt[0])
     else:
         dec = _Decoder(model, gc, B, Tk, P, ml, rq.timestamps, rq.use_graph, repetition_penalty=rq.repetition_penalty,
-                       no_repeat_ngram_size=rq.no_repeat_ngram_size)
+                       no_repeat_ngram_size=rq.no_repeat_ngram_size, **lpkw)
         if rq.keep is not None:              # tests: the decoder (and its device caches) outlive the call
             rq.keep.append(dec)
         out = dec.run(enc16, prompt.to(dev), **(dict(detect=detect) if fused else {}))
         if fused and rq.return_language:
             lang_out = dec.sel.ids[:, 1].clone()
+    if want_lp:        # a decoder built with logp returns (ids, log-probs); nothing decoded: no columns
+        out, lps = out if isinstance(out, tuple) else (out, torch.zeros(B, 0, dtype=torch.float32, device=dev))
+        return (out, lang_out, lps.clone()) if rq.return_language else (out, lps.clone())
     return (out, lang_out) if rq.return_language else out
 
 
@@ -1152,7 +1191,8 @@ class _LongForm:
     def decoder(self, P, ml, nb=1, spec=False):
         # the two repeat options and the models' cross-attention K/V format are baked into a captured step
         key = (P, ml, nb, spec, self.rq.repetition_penalty, self.rq.no_repeat_ngram_size,
-               getattr(self.model, "cross_kv_dtype", None), getattr(self.rq.assistant, "cross_kv_dtype", None))
+               getattr(self.model, "cross_kv_dtype", None), getattr(self.rq.assistant, "cross_kv_dtype", None),
+               self.rq.return_token_logprobs)
         if key in self.decoders:
             self.decoders[key] = self.decoders.pop(key)      # most recently used last
         else:
@@ -1161,13 +1201,14 @@ class _LongForm:
             while len(self.decoders) >= 3:
                 self.decoders.pop(next(iter(self.decoders)))
             m, Tk = self.model, self.model.config.max_source_positions
+            lpkw = dict(logp=True) if self.rq.return_token_logprobs else {}
             if spec:
                 self.decoders[key] = _SpecDecoder(m, self.rq.assistant, self.gc, Tk, P, ml, True, self.rq.use_graph,
-                                                  self.rq.track, k=self.rq.k)
+                                                  self.rq.track, k=self.rq.k, **lpkw)
             else:
                 self.decoders[key] = _Decoder(m, self.gc, nb, Tk, P, ml, True, self.rq.use_graph, self.rq.track,
                                               repetition_penalty=self.rq.repetition_penalty,
-                                              no_repeat_ngram_size=self.rq.no_repeat_ngram_size)
+                                              no_repeat_ngram_size=self.rq.no_repeat_ngram_size, **lpkw)
         return self.decoders[key]
 
     def seeds(self, b, nwin):
@@ -1177,7 +1218,8 @@ class _LongForm:
 
     # One attempt of the fallback ladder on the window state w (enc, enc_a, prompts, P, ml, ns, seeds, padded) ->
     # (raw tokens per attempt, gate(r, n) -> (avg_logprob over n tokens, no_speech_prob) of row r, read back only when
-    # the row is gated, decode batch, accepted drafts per round or None)
+    # the row is gated, decode batch, accepted drafts per round or None, the log-prob of every raw token per attempt
+    # or None without return_token_logprobs)
     def decode_rows(self, w, attempts):
         """`attempts` [(recording, level)] as one batch of _bucket rows, each with its own temperature and seed; rows
         of one window share its encoder rows (K/V projected once).  A group of several conditioned recordings passes
@@ -1200,12 +1242,15 @@ class _LongForm:
         if assisted:
             kw["enc_a"] = w.enc_a[b0]
         # a batch is cut at its LAST row's first eos: each row is cut at its own first eos, what its own decode returns
-        raws = [row_tokens(r, self.eos) for r in dec.run(e16, prompt, **kw).tolist()[:len(attempts)]]
+        out = dec.run(e16, prompt, **kw)
+        ids, lpm = out if self.rq.return_token_logprobs else (out, None)
+        raws = [row_tokens(r, self.eos) for r in ids.tolist()[:len(attempts)]]
+        lps = None if lpm is None else [lp[:len(raw)] for lp, raw in zip(lpm.tolist(), raws)]
 
         def gate(r, n):
             return (float(dec.sel.sum_logp[r]) / n if self.rq.track else 0.0,
                     float(torch.exp(dec.ns_logp[r])) if w.ns is not None else 0.0)
-        return raws, gate, nb, list(dec.accepted) if assisted else None
+        return raws, gate, nb, list(dec.accepted) if assisted else None, lps
 
     def decode_beam(self, w, b):
         """HF generate_with_fallback at temperature 0 with num_beams > 1: a beam search over recording b's window
@@ -1220,10 +1265,12 @@ class _LongForm:
 
         def gate(r, n):
             return float(bd.sum_logp[0]) / n, float(bd.ns_prob[0]) if w.ns is not None else 0.0
-        return [raw], gate, 1, None
+        return [raw], gate, 1, None, None
 
     def run(self, feats, lens, recs):
-        """The seek loop over the recordings `recs` (their indices in the call) -> {recording: its tokens}."""
+        """The seek loop over the recordings `recs` (their indices in the call) -> ({recording: its tokens},
+        {recording: their log-probs} -- with return_token_logprobs; every cut of an attempt's tokens below cuts its
+        log-probs at the same indices, so a token keeps the value of the attempt that was kept)."""
         model, rq, eos, pad = self.model, self.rq, self.eos, self.pad
         temps, trace, cond = rq.temps, rq.trace, rq.condition_on_prev_tokens
         window = 2 * model.config.max_source_positions            # 3000 feature frames = 30 s
@@ -1235,6 +1282,7 @@ class _LongForm:
         seek = {b: 0 for b in recs}
         nwin = {b: 0 for b in recs}
         outs = {b: [] for b in recs}
+        out_lps = {b: [] for b in recs}
         segments = {b: [] for b in recs}         # accepted segments per recording (the previous text)
         cond_on = {b: cond for b in recs}
         while True:
@@ -1273,7 +1321,8 @@ class _LongForm:
                 levels = list(range(level, min(len(temps), level + per)))
                 attempts = [(b, f) for f in levels for b in pending]
                 beam = rq.num_beams > 1 and len(levels) == 1 and not temps[level]
-                raws, gate, batch, accepted = self.decode_beam(w, pending[0]) if beam else self.decode_rows(w, attempts)
+                raws, gate, batch, accepted, lps = (self.decode_beam(w, pending[0]) if beam
+                                                    else self.decode_rows(w, attempts))
                 decided = set()
                 for r, (b, f) in enumerate(attempts):
                     if b in decided:
@@ -1293,16 +1342,18 @@ class _LongForm:
                         rec["batch"] = batch
                     if accepted is not None:
                         rec["accepted"] = accepted
+                    if lps is not None:
+                        rec["token_logprobs"] = list(lps[r])          # one per token of `raw`
                     if trace is not None:
                         trace.append(rec)
-                    result[b] = (raw, skip, temps[f])
+                    result[b] = (raw, skip, temps[f], lps[r] if lps is not None else None)
                     if not needs:
                         decided.add(b)
                 pending = [b for b in pending if b not in decided]
                 level = levels[-1] + 1
             del w
             for b in active:
-                seq, skip, t_acc = result[b]
+                seq, skip, t_acc, lp = result[b]
                 n = nfr[b]
                 nwin[b] += 1
                 cond_on[b] = cond and (t_acc is None or t_acc < 0.5)
@@ -1318,8 +1369,11 @@ class _LongForm:
                     outs[b].extend(sgm)
                     if cond:
                         segments[b].append(list(sgm))
+                if lp is not None:                        # seq is a prefix of the attempt's tokens
+                    for sl in segment_logprobs(lp[:len(seq)], segs):
+                        out_lps[b].extend(sl)
                 seek[b] += off if off > 0 else n          # a closing <|0.00|> pair would not advance: take the window
-        return outs
+        return outs, out_lps
 
 
 def _longform(model, gc, rq, feats, attention_mask):
@@ -1335,7 +1389,7 @@ def _longform(model, gc, rq, feats, attention_mask):
     rq: the call's Request.  Its languages give every recording its own task prompt for all of its windows; "auto"
     detects once per call, as HF does, on the first 3000 raw frames of every recording (HF's
     input_features[:, :, :3000], not the zero-filled window the seek loop cuts), enc_rows recordings at a time.
-    rq.return_language: -> (ids, language ids int64 [B])."""
+    rq.return_language: -> (ids, language ids int64 [B]); rq.return_token_logprobs: the ids' log-probs last."""
     cfg = model.config
     feats = feats.to(model.device, torch.float32)
     B, _, T = feats.shape
@@ -1361,13 +1415,21 @@ def _longform(model, gc, rq, feats, attention_mask):
                    # prompt_ids: in front of every window's task prompt
                    init=[list(rq.prompt_ids or ()) + t for t in task_inits],
                    n_task=len(task_inits[0]) if task_inits else 0)
-    outs = {}
+    outs, out_lps = {}, {}
     for recs in ([list(range(B))] if rq.num_beams == 1 else [[b] for b in range(B)]):
-        outs.update(lf.run(feats, lens, recs))
+        o, l = lf.run(feats, lens, recs)
+        outs.update(o)
+        out_lps.update(l)
     L = max((len(o) for o in outs.values()), default=0)
     res = torch.full((B, L), pad, dtype=torch.int64)
     for b, o in outs.items():
         res[b, :len(o)] = torch.tensor(o, dtype=torch.int64)
+    ret = [res.to(model.device)]
     if rq.return_language:
-        return res.to(model.device), torch.tensor(langs, dtype=torch.int64, device=model.device)
-    return res.to(model.device)
+        ret.append(torch.tensor(langs, dtype=torch.int64, device=model.device))
+    if rq.return_token_logprobs:            # the ids' shape; 0 in the padding between rows
+        lps = torch.zeros(B, L, dtype=torch.float32)
+        for b, l in out_lps.items():
+            lps[b, :len(l)] = torch.tensor(l, dtype=torch.float32)
+        ret.append(lps.to(model.device))
+    return tuple(ret) if len(ret) > 1 else ret[0]

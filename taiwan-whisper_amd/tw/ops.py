@@ -626,9 +626,11 @@ def embed_step_multi(ids, tok, pos, out, t_dev, Q):
 
 
 def spec_accept(drafts, k, ids_row, t_cap, eos, t_dev, cur, done, done_snap, *, t_dev_a=None, cur_a=None, done_a=None,
-                last_ts=None, last_ts_a=None, begin_col=0, ts_begin=0, slots=None, sum_logp=None, hist=None):
+                last_ts=None, last_ts_a=None, begin_col=0, ts_begin=0, slots=None, sum_logp=None, hist=None,
+                tok_logp=None):
     """tw_spec_accept on one row (include/tw_hip.h): ids_row is that row of the id matrix and holds at least
-    t_cap + k + 1 columns, so a round that starts at the last column t_cap - 1 stays inside it."""
+    t_cap + k + 1 columns, so a round that starts at the last column t_cap - 1 stays inside it.  tok_logp: the same
+    row of the per-token log-prob matrix (float32, as many columns; needs slots) -> tw_spec_accept_lp."""
     assert drafts.dtype == torch.int64 and ids_row.dtype == torch.int64 and ids_row.dim() == 1
     assert ids_row.stride(0) == 1 and cur.dtype == torch.int64 and 1 <= k < MQ_MAX
     _need(drafts, k, "spec_accept drafts")
@@ -648,6 +650,15 @@ def spec_accept(drafts, k, ids_row, t_cap, eos, t_dev, cur, done, done_snap, *, 
         assert hist.dtype == torch.int32 and hist.is_contiguous()
         hist_cap = hist.numel()
         _need(hist, hist_cap, "spec_accept hist")
+    if tok_logp is not None:
+        assert tok_logp.dtype == torch.float32 and tok_logp.dim() == 1 and tok_logp.stride(0) == 1
+        assert slots is not None and tok_logp.device == ids_row.device
+        _need(tok_logp, t_cap + k + 1, "spec_accept tok_logp")
+        call("tw_spec_accept_lp", drafts.data_ptr(), int(k), ids_row.data_ptr(), int(t_cap), int(eos),
+             t_dev.data_ptr(), _ptr(t_dev_a), cur.data_ptr(), _ptr(cur_a), done.data_ptr(), _ptr(done_a),
+             done_snap.data_ptr(), _ptr(last_ts), _ptr(last_ts_a), int(begin_col), int(ts_begin), _ptr(slots),
+             _ptr(sum_logp), tok_logp.data_ptr(), _ptr(hist), hist_cap, _stream())
+        return
     call("tw_spec_accept", drafts.data_ptr(), int(k), ids_row.data_ptr(), int(t_cap), int(eos), t_dev.data_ptr(),
          _ptr(t_dev_a), cur.data_ptr(), _ptr(cur_a), done.data_ptr(), _ptr(done_a), done_snap.data_ptr(),
          _ptr(last_ts), _ptr(last_ts_a), int(begin_col), int(ts_begin), _ptr(slots), _ptr(sum_logp), _ptr(hist),
@@ -666,9 +677,10 @@ def token_bitmask(ids, V, device):
 
 
 def _select_args(what, logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, last_ts=None,
-                 ctl=None, sum_logp=None):
+                 ctl=None, sum_logp=None, tok_logp=None):
     """The checks the four selection wrappers share: dtypes and extents of the logits, the id matrix (every column
-    when the column comes from the device), the flags, the masks and, where given, last_ts / ctl / sum_logp."""
+    when the column comes from the device), the flags, the masks and, where given, last_ts / ctl / sum_logp /
+    tok_logp (the per-token matrix: the id matrix's columns, its own row stride; sum_logp may then be None)."""
     assert logits.dtype in (torch.bfloat16, torch.float16, torch.float32) and ids.dtype == torch.int64
     assert next_ids.dtype == torch.int64 and done.dtype == torch.uint8
     _need(logits, (B - 1) * ld + V, f"{what} logits")
@@ -681,8 +693,18 @@ def _select_args(what, logits, ld, B, V, suppress_bits, begin_bits, done, ids, c
         assert last_ts.dtype == torch.int32
         _need(last_ts, B, f"{what} last_ts")
     if ctl is not None:
-        assert ctl.dtype == torch.int32 and ctl.numel() >= 3 * B and sum_logp.dtype == torch.float32
-        _need(sum_logp, B, f"{what} sum_logp")
+        assert ctl.dtype == torch.int32 and ctl.numel() >= 3 * B
+        assert sum_logp is not None or tok_logp is not None
+        if sum_logp is not None:
+            assert sum_logp.dtype == torch.float32
+            _need(sum_logp, B, f"{what} sum_logp")
+    if tok_logp is not None:
+        assert tok_logp.dtype == torch.float32 and tok_logp.dim() == 2 and tok_logp.stride(1) == 1
+        assert tok_logp.device == logits.device and tok_logp.shape[0] >= B
+        ncol = ids.shape[1] if t_dev is not None else col + 1
+        if tok_logp.shape[1] < ncol:
+            raise ValueError(f"tw: {what} tok_logp {tuple(tok_logp.shape)} holds no column {ncol - 1}")
+        _need(tok_logp, (B - 1) * tok_logp.stride(0) + ncol, f"{what} tok_logp")
 
 
 def greedy_select(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, col, next_ids,
@@ -704,22 +726,37 @@ def greedy_select_ts(logits, ld, B, V, suppress_bits, begin_bits, eos, done, ids
 
 
 def select_sample(logits, ld, B, V, suppress_bits, begin_bits, apply_begin, eos, done, ids, col, next_ids, ctl,
-                  sum_logp, t_dev=None, begin_col=-1):
+                  sum_logp, t_dev=None, begin_col=-1, tok_logp=None):
     """greedy_select + temperature sampling (ctl: int32[3B], per row bits(1/T), seed lo, hi; 1/T = 0 -> argmax)
-    + running log-prob of the chosen token (sum_logp: float32[B])."""
+    + running log-prob of the chosen token (sum_logp: float32[B]).  tok_logp (float32 [B, >= the id matrix's
+    columns]): tw_select_sample_lp, which also stores that log-prob at the token's column (0 for a row already
+    finished); sum_logp may then be None."""
     assert ctl is not None
     _select_args("select", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, None, ctl,
-                 sum_logp)
+                 sum_logp, tok_logp)
+    if tok_logp is not None:
+        call("tw_select_sample_lp", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits),
+             int(apply_begin), int(eos), done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(),
+             _ptr(t_dev), int(begin_col), ctl.data_ptr(), _ptr(sum_logp), tok_logp.data_ptr(), tok_logp.stride(0),
+             _stream())
+        return
     call("tw_select_sample", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(apply_begin),
          int(eos), done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev),
          int(begin_col), ctl.data_ptr(), sum_logp.data_ptr(), _stream())
 
 
 def select_sample_ts(logits, ld, B, V, suppress_bits, begin_bits, eos, done, ids, col, next_ids, last_ts, begin_col,
-                     ctl, sum_logp, ts_begin=50364, no_ts=50363, max_initial=-1, t_dev=None):
+                     ctl, sum_logp, ts_begin=50364, no_ts=50363, max_initial=-1, t_dev=None, tok_logp=None):
+    """select_sample with the timestamp rules (tw_select_sample_ts; with tok_logp tw_select_sample_ts_lp)."""
     assert last_ts is not None and ctl is not None
     _select_args("select", logits, ld, B, V, suppress_bits, begin_bits, done, ids, col, next_ids, t_dev, last_ts, ctl,
-                 sum_logp)
+                 sum_logp, tok_logp)
+    if tok_logp is not None:
+        call("tw_select_sample_ts_lp", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits),
+             _ptr(begin_bits), int(eos), done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(),
+             _ptr(t_dev), int(begin_col), int(ts_begin), int(no_ts), int(max_initial if max_initial is not None else -1),
+             last_ts.data_ptr(), ctl.data_ptr(), _ptr(sum_logp), tok_logp.data_ptr(), tok_logp.stride(0), _stream())
+        return
     call("tw_select_sample_ts", logits.data_ptr(), ld, _dt(logits), B, V, _ptr(suppress_bits), _ptr(begin_bits), int(eos),
          done.data_ptr(), ids.data_ptr(), ids.stride(0), col, next_ids.data_ptr(), _ptr(t_dev), int(begin_col),
          int(ts_begin), int(no_ts), int(max_initial if max_initial is not None else -1), last_ts.data_ptr(),

@@ -20,7 +20,10 @@ Differences, by design or by what this image lacks (each stated where it applies
     chunk zero-padded to 30 s before the STFT), the arithmetic the decode tests pin to HF;
   * text: `tokenizers.Tokenizer.from_file(<model dir>/tokenizer.json)` decode of the ids below
     <|endoftext|> (faster-whisper Tokenizer.decode); without that file, --byte_level_text_tokenizer
-    decodes ids < 256 as UTF-8 bytes (tests only).
+    decodes ids < 256 as UTF-8 bytes (tests only);
+  * --write_scores (off by default: the CSV is the reference's) adds avg_logprob, min_logprob and
+    compression_ratio per row, the numbers faster-whisper's segments carry and the reference's prefiltering
+    stage has to do without; --min_avg_logprob drops the rows below a threshold.
 """
 from __future__ import annotations
 
@@ -68,7 +71,15 @@ def parse_args(argv=None):
     ap.add_argument("--cross_kv_dtype", type=str, default="auto", choices=["auto", "fp8_e4m3"],
                     help="cross-attention K/V cache: auto -> the compute type's 16 bits; fp8_e4m3 -> 8-bit blocks with "
                          "power-of-two scales (half the memory and bytes per token; not with float32)")
-    return ap.parse_args(argv)
+    ap.add_argument("--write_scores", type=_bool, default=False,
+                    help="add the columns avg_logprob, min_logprob, compression_ratio after text (avg_logprob: "
+                         "faster-whisper's, the mean log-prob of the chunk's generated tokens, eos included)")
+    ap.add_argument("--min_avg_logprob", type=float, default=None,
+                    help="with --write_scores: drop the rows whose avg_logprob is below this")
+    args = ap.parse_args(argv)
+    if args.min_avg_logprob is not None and not args.write_scores:
+        ap.error("--min_avg_logprob needs --write_scores True")
+    return args
 
 
 def load_dataset(dataset_path: str) -> List[str]:
@@ -92,10 +103,25 @@ def chunk_audio(wav: np.ndarray, sr: int, chunk_length: float) -> List[Tuple[flo
     return out
 
 
-def save_transcription_to_csv(rows: Sequence[dict], output_csv: str):
-    """initial_inference.py:48-54."""
+SCORE_COLUMNS = ["avg_logprob", "min_logprob", "compression_ratio"]
+
+
+def chunk_scores(ids: Sequence[int], logprobs: Sequence[float], vocab_size: int) -> dict:
+    """The score columns of one chunk.  logprobs: one value per generated token up to and including eos (`ids` is
+    that row without its eos).  avg_logprob: their sum over their count (faster-whisper's segment.avg_logprob, as
+    HF's fallback gate averages it); min_logprob: the least of them; compression_ratio: generation.compression_ratio
+    of the ids.  A chunk with no generated token scores 0.0."""
+    from .generation import compression_ratio
+    lps = [float(x) for x in logprobs]
+    n = len(lps)
+    return {"avg_logprob": sum(lps) / n if n else 0.0, "min_logprob": min(lps) if n else 0.0,
+            "compression_ratio": compression_ratio(ids, vocab_size) if len(ids) else 0.0}
+
+
+def save_transcription_to_csv(rows: Sequence[dict], output_csv: str, scores: bool = False):
+    """initial_inference.py:48-54; scores: the SCORE_COLUMNS after text."""
     with open(output_csv, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=["start", "end", "text"])
+        w = csv.DictWriter(f, fieldnames=["start", "end", "text"] + (SCORE_COLUMNS if scores else []))
         w.writeheader()
         for r in rows:
             w.writerow(r)
@@ -103,7 +129,10 @@ def save_transcription_to_csv(rows: Sequence[dict], output_csv: str):
 
 class ChunkTranscriber:
     """Batched greedy transcription of <= 30 s chunks: GPU log-mel of the zero-padded chunk, encoder,
-    KV-cache greedy decode.  Returns the generated ids per chunk (eos and padding removed)."""
+    KV-cache greedy decode.  Returns the generated ids per chunk (eos and padding removed); with the attribute
+    return_scores set (the driver's --write_scores; the constructor keeps its signature) (ids, log-probs of the
+    generated tokens up to and including eos) per chunk (generate's return_token_logprobs)."""
+    return_scores = False
 
     def __init__(self, model, language: str = "zh", max_new_tokens: Optional[int] = None, device=None,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0):
@@ -123,11 +152,13 @@ class ChunkTranscriber:
         mel, _ = self.fe.extract(wav, want_conv_input=False)
         ids = self.m.generate(mel, language=self.language, task="transcribe", max_new_tokens=self.max_new_tokens,
                               repetition_penalty=self.repetition_penalty,
-                              no_repeat_ngram_size=self.no_repeat_ngram_size)
+                              no_repeat_ngram_size=self.no_repeat_ngram_size,
+                              **(dict(return_token_logprobs=True) if self.return_scores else {}))
+        ids, lps = ids if self.return_scores else (ids, None)
         out = []
-        for row in ids.tolist():
+        for r, row in enumerate(ids.tolist()):
             k = row.index(self.eot) if self.eot in row else len(row)
-            out.append(row[:k])
+            out.append((row[:k], lps[r, :k + 1].tolist()) if self.return_scores else row[:k])
         return out
 
 
@@ -136,14 +167,23 @@ def transcribe_files(paths: Sequence[str], transcribe: Callable[[Sequence[np.nda
                      read_audio: Callable[[str], Tuple[np.ndarray, int]], num_workers: int = 8,
                      log: Callable[[str], None] = print,
                      on_done: Optional[Callable[[str, List[dict]], None]] = None,
-                     max_ahead: Optional[int] = None) -> Dict[str, Optional[List[dict]]]:
+                     max_ahead: Optional[int] = None, scores: bool = False, vocab_size: int = 51865,
+                     min_avg_logprob: Optional[float] = None,
+                     stats: Optional[dict] = None) -> Dict[str, Optional[List[dict]]]:
     """-> {path: rows or None (missing / failed file)}.  Files are decoded on `num_workers` host threads
     ahead of the GPU, at most `max_ahead` (default 2 x num_workers) files in flight, so host memory holds a
     bounded number of decoded waveforms whatever the manifest size; chunks of consecutive files fill
     batches of `batch_size` across file boundaries.  `on_done(path, rows)` runs as soon as a file's last
     chunk is transcribed (the reference writes each CSV when its file finishes, initial_inference.py:106-
     115).  A batch whose transcription or text decoding raises is retried one file at a time; a file whose own
-    chunks raise is failed (logged, result None, its other chunks dropped) and the run goes on (:116-119)."""
+    chunks raise is failed (logged, result None, its other chunks dropped) and the run goes on (:116-119).
+    scores: `transcribe` returns (ids, log-probs up to and including eos) per chunk (ChunkTranscriber with
+    return_scores) and every row gains chunk_scores' columns, formatted "%.4f"; min_avg_logprob then drops the rows
+    whose avg_logprob is below it, counted in stats["dropped"] (stats["rows"]: the rows kept)."""
+    assert min_avg_logprob is None or scores
+    stats = {} if stats is None else stats
+    stats.update(rows=0, dropped=0)
+    seen: Dict[str, int] = {}
     results: Dict[str, Optional[List[dict]]] = {}
     pending: List[Tuple[str, float, float, np.ndarray]] = []
     counts: Dict[str, int] = {}
@@ -159,11 +199,14 @@ def transcribe_files(paths: Sequence[str], transcribe: Callable[[Sequence[np.nda
             log(f"Failed to transcribe {p}, error: {e}")
             rows.pop(p, None)
             counts.pop(p, None)
+            seen.pop(p, None)
             results[p] = None
         pending[:] = [c for c in pending if c[0] not in set(bad)]
 
     def run(batch):
         toks = transcribe([c[3] for c in batch])
+        if scores:      # (text, score columns) per chunk
+            return [(decode(t), chunk_scores(t, lp, vocab_size)) for t, lp in toks]
         return [decode(t) for t in toks]
 
     def flush(force=False):
@@ -189,9 +232,19 @@ def transcribe_files(paths: Sequence[str], transcribe: Callable[[Sequence[np.nda
             for (p, s, e, _), t in done:
                 if p not in rows:               # failed in an earlier batch
                     continue
-                rows[p].append({"start": f"{s:.2f}", "end": f"{e:.2f}", "text": t})
-                if len(rows[p]) == counts[p]:
+                seen[p] += 1
+                if scores:
+                    t, sc = t
+                if scores and min_avg_logprob is not None and sc["avg_logprob"] < min_avg_logprob:
+                    stats["dropped"] += 1
+                else:
+                    rows[p].append({"start": f"{s:.2f}", "end": f"{e:.2f}", "text": t})
+                    if scores:
+                        rows[p][-1].update({k: f"{v:.4f}" for k, v in sc.items()})
+                    stats["rows"] += 1
+                if seen[p] == counts[p]:
                     counts.pop(p)
+                    seen.pop(p)
                     finish(p, rows.pop(p))
 
     def load(p):
@@ -231,7 +284,7 @@ def transcribe_files(paths: Sequence[str], transcribe: Callable[[Sequence[np.nda
             if not chunks:
                 finish(p, [])
                 continue
-            counts[p], rows[p] = len(chunks), []
+            counts[p], rows[p], seen[p] = len(chunks), [], 0
             pending.extend((p, s, e, w) for s, e, w in chunks)
             del chunks
             flush()
@@ -270,16 +323,24 @@ def main(argv=None):
     decode = load_text_decoder(args)
     tr = ChunkTranscriber(model, args.language, args.max_new_tokens, repetition_penalty=args.repetition_penalty,
                           no_repeat_ngram_size=args.no_repeat_ngram_size)
+    tr.return_scores = bool(args.write_scores)
     paths = load_dataset(args.dataset_path)[rank::world]
     os.makedirs(args.output_dir, exist_ok=True)
+    stats = {}
+
     def write(p, r):
         out = os.path.join(args.output_dir, os.path.splitext(os.path.basename(p))[0] + ".csv")
-        save_transcription_to_csv(r, out)
+        save_transcription_to_csv(r, out, **(dict(scores=True) if args.write_scores else {}))
         print(f"Transcription completed: {out}", flush=True)
 
     res = transcribe_files(paths, tr, decode, args.chunk_length, args.batch_size, read_audio, args.num_workers,
                            log=(lambda s: print(s, flush=True)) if args.log_progress else (lambda s: None),
-                           on_done=write)
+                           on_done=write,
+                           **(dict(scores=True, vocab_size=model.config.vocab_size,
+                                   min_avg_logprob=args.min_avg_logprob, stats=stats) if args.write_scores else {}))
+    if args.write_scores:
+        cut = "" if args.min_avg_logprob is None else f" below --min_avg_logprob {args.min_avg_logprob}"
+        print(f"Scores written: {stats['rows']} rows kept, {stats['dropped']} rows dropped{cut}", flush=True)
     return res
 
 
