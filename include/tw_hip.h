@@ -480,6 +480,42 @@ int tw_decode_attn_mq_fp8(const void* q, int64_t sqb, int64_t sqq, const void* k
                           int Tk, const int* tk_dev, const int* k_start, int causal, int head_dim, float scale,
                           int dtype, tw_stream_t stream);
 
+/* ---- 8-bit decoder weights for the batch <= 8 decode step (model.decode_weight_dtype = "fp8_e4m3";
+ * csrc/gemv_w8.hip).  Opt-in: at batch <= 8 every Linear of a decode step is one GEMV launch that streams its weight
+ * matrix once per generated token; as bytes the matrix is half as large.
+ * FORMAT.  A weight matrix W [N][K] (16-bit, row-major, one output column per row) is kept as N*K OCP e4m3fn bytes
+ * (torch.float8_e4m3fn), rounded to nearest even, row n at byte n*ld, plus one fp32 scale per row: N floats.  The
+ * scale rule is the K/V format's above with "block" = one row of K values: a scale is 2^e, e the smallest integer
+ * with absmax(row) * 2^-e <= 448 (absmax = m * 2^x, m in [0.5, 1): e = x - 9 when m <= 0.875, else x - 8), e
+ * clamped to [-100, 100]; an all-zero row gets 1; a row holding an inf or NaN gets a NaN scale, so exactly that
+ * output column is NaN.  A byte is RNE_e4m3(x * 2^-e): the product is exact and at most 448 in magnitude.
+ * Dequantisation (byte * 2^e) is exact: the value has at most 4 significant bits, so it is a bf16 value, and it is
+ * an fp16 value wherever it is a multiple of 2^-24 (fp16's smallest subnormal: a byte stands for a multiple of
+ * 2^(e-9), so only rows with e < -15, absmax below 2^-6, can leave that grid) and at most 65504 in magnitude (an fp16
+ * row whose absmax is 63488 = 248 * 2^8 or more rounds it up to 256 * 2^8 = 65536).  Whisper weights are inside both limits.
+ * tw_quant_rows_fp8: rows src [N][ld] of `dtype` (bf16 or fp16; fp32: 2) -> bytes dst_bytes [N][ld_dst] and
+ * scales [N].  One wave per row, two passes (absmax, quantise).  A null pointer, a pointer not 16-B aligned (scales:
+ * 4-B), K % 16 != 0, ld or ld_dst below K or not a multiple of 16 B: 1.
+ * tw_gemv_w8_bf16 / tw_gemv_w8_f16: tw_gemv_bf16 / tw_gemv_f16 over such a matrix, their contract in full (M <= 8
+ * rows, optional fused LayerNorm with A bit-identical to tw_layernorm_fwd's output, the bias / round / GELU (+ aux
+ * out) / residual / accumulate epilogues, fp32 or 16-bit C, the fused self-attention KV append) with these
+ * differences: W points at bytes, ldw counts bytes and is a multiple of 16, K % 16 == 0, and w_scale holds the N row
+ * scales (a null w_scale returns 1).  The bytes are converted to fp32 exactly and accumulated in fp32 (16 bytes = 16 k per lane per
+ * load, lane l holding k = 16 l + 1024 u); the row's scale multiplies the reduced sum once, before the epilogue --
+ * exact, a power of two -- so the result is the fp32 arithmetic of a GEMV over the dequantised matrix, in another
+ * summation order than tw_gemv_bf16's.  Row m of an M-row call is bit-identical to that row computed with M = 1, and
+ * the LN-fused call to tw_layernorm_fwd followed by the plain call. */
+int tw_quant_rows_fp8(const void* src, int64_t ld, int dtype, int N, int K, void* dst_bytes, int64_t ld_dst,
+                      float* scales, tw_stream_t stream);
+int tw_gemv_w8_bf16(const void* x, int64_t ldx, const float* ln_w, const float* ln_b, float eps, const void* W,
+                    int64_t ldw, const float* w_scale, void* C, int64_t ldc, int c_dtype, int M, int N, int K,
+                    const void* bias, const void* res, int64_t ldr, int res_dtype, void* aux, int64_t ldaux, int flags,
+                    void* kv_cache, int64_t kv_sb, int64_t kv_ld, int kv_col0, const int* t_dev, tw_stream_t stream);
+int tw_gemv_w8_f16(const void* x, int64_t ldx, const float* ln_w, const float* ln_b, float eps, const void* W,
+                   int64_t ldw, const float* w_scale, void* C, int64_t ldc, int c_dtype, int M, int N, int K,
+                   const void* bias, const void* res, int64_t ldr, int res_dtype, void* aux, int64_t ldaux, int flags,
+                   void* kv_cache, int64_t kv_sb, int64_t kv_ld, int kv_col0, const int* t_dev, tw_stream_t stream);
+
 /* ---- fp32 arithmetic path (mixed_precision = "no", run_distillation.py:815-823: the reference's default
  * --dtype float32; the fp32 greedy decode pinned token-for-token to HF fp32 generate).  Exact-fp32 MFMA
  * (v_mfma_f32_16x16x4_f32), nothing rounded to bf16.

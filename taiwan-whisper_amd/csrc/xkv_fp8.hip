@@ -17,45 +17,16 @@
 //    the split rule are those of decode.hip.
 #include "common.h"
 #include "decode_impl.h"
+#include "fp8_common.h"
 
 #include <algorithm>
 
 namespace {
 
 using namespace twd;
+using namespace tw8;   // cvt4_e4m3 / words_f32 / scale_exp
 
 // ------------------------------------------------------------------------------------------------ quantiser
-// RNE of y (|y| <= 448 or NaN) to e4m3fn by the hardware conversion: two values into one half of a dword
-__device__ __forceinline__ uint32_t cvt4_e4m3(float a, float b, float c, float d) {
-  int w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);
-  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-  return (uint32_t)w;
-}
-
-// 8 consecutive 16-bit words (one 16-B load) as fp32
-template <bool H>
-__device__ __forceinline__ void words_f32(const bf16x8 v, float* o) {
-  if constexpr (H) {
-    const f16x8 h = __builtin_bit_cast(f16x8, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (float)h[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = bf2f(v[j]);
-  }
-}
-
-// scale exponent of a block from the fp32 bits of its absmax (finite, > 0): absmax = m * 2^x, m in [0.5, 1);
-// e = x - 9 when m <= 0.875 (then absmax * 2^-e <= 0.875 * 512 = 448), else x - 8; fp32 subnormals sit far
-// below the clamp
-__device__ __forceinline__ int scale_exp(uint32_t u) {
-  const int ef = (int)(u >> 23);
-  if (ef == 0) return -100;
-  const int x = ef - 126;
-  const int e = (u & 0x7fffffu) <= 0x600000u ? x - 9 : x - 8;
-  return max(-100, min(100, e));
-}
-
 // grid = 2 * B * H workgroups: block (part = K / V, b, h)
 template <bool H>
 __global__ __launch_bounds__(256) void kv_head_major_fp8_kernel(const bf16* __restrict__ src, int64_t ld,

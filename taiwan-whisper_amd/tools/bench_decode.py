@@ -5,10 +5,11 @@ synthetic 30 s features; eos is suppressed so every clip runs exactly --new-toke
     python tools/bench_decode.py [--batch 64] [--new-tokens 224] [--clips 128] [--eager] [--dtype float16]
                                  [--repetition_penalty 1.3] [--no_repeat_ngram_size 3]
                                  [--language zh | auto | zh,en,...] [--runs 5] [--detect]
-                                 [--return_token_logprobs]
+                                 [--return_token_logprobs] [--decode_weight_dtype fp8_e4m3]
 --language auto detects every clip's language (generate(language="auto")); a comma list names one language per clip
 (repeated to the batch).  --runs N times N calls and prints each; --detect times detect_language alone instead.
 --return_token_logprobs decodes with generate(return_token_logprobs=True) (the tracking selectors' _lp entries).
+--decode_weight_dtype fp8_e4m3 decodes over 8-bit decoder weights (model.decode_weight_dtype; tw_gemv_w8_* at batch <= 8).
 """
 import argparse
 import os
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--detect", action="store_true", help="time detect_language alone (with --runs)")
     ap.add_argument("--return_token_logprobs", action="store_true",
                     help="generate(return_token_logprobs=True): per-token log-probs beside the ids")
+    ap.add_argument("--decode_weight_dtype", default="auto", choices=["auto", "fp8_e4m3"],
+                    help="model.decode_weight_dtype: the decode step's Linear weights as e4m3 bytes with row scales")
     ap.add_argument("--longform-seconds", type=float, default=0.0,
                     help="config c5: one input of this many seconds, return_timestamps, --new-tokens per window")
     a = ap.parse_args()
@@ -46,6 +49,7 @@ def main():
     if a.dtype == "float16":
         m.set_compute("fp16")
     random_init_(m, seed=0)
+    m.decode_weight_dtype = a.decode_weight_dtype
     m.generation_config = GenerationConfig(suppress_tokens=[50257], begin_suppress_tokens=[220, 50257],
                                            lang_to_id={"<|zh|>": 50260})
     if a.language != "zh":      # large-v2's 99 language ids, so that detection has its real table
@@ -95,6 +99,7 @@ def main():
         what = "detect_language" if a.detect else (f"generate language={a.language} {a.new_tokens} tokens"
                                                    f"{' token_logprobs' if a.return_token_logprobs else ''}")
         per = "" if a.detect else f", median {sorted(ms)[len(ms) // 2] / a.new_tokens:.3f} ms/step"
+        what += "" if a.decode_weight_dtype == "auto" else f" weights {a.decode_weight_dtype}"
         print(f"{what} {a.config} {a.dtype} batch {a.batch}: per call ms {' '.join(f'{x:.2f}' for x in ms)} "
               f"(min {min(ms):.2f}, median {sorted(ms)[len(ms) // 2]:.2f}, max {max(ms):.2f}{per})", flush=True)
         return

@@ -100,6 +100,13 @@ SIGNATURES = {
                            F32, I32, P],
     "tw_decode_attn_mq_fp8": [P, I64, I64, P, I64, I64, I64, P, I64, I64, I64, P, P, I64, P, I64, I64, I32, I32, I32,
                               I32, P, P, I32, I32, F32, I32, P],
+    # 8-bit decoder weights (decode_weight_dtype="fp8_e4m3"): the row quantiser and the batch <= 8 GEMV over bytes
+    # (tw_gemv_bf16's arguments with w_scale after ldw)
+    "tw_quant_rows_fp8": [P, I64, I32, I32, I32, P, I64, P, P],
+    "tw_gemv_w8_bf16": [P, I64, P, P, F32, P, I64, P, P, I64, I32, I32, I32, I32, P, P, I64, I32, P, I64, I32,
+                        P, I64, I64, I32, P, P],
+    "tw_gemv_w8_f16": [P, I64, P, P, F32, P, I64, P, P, I64, I32, I32, I32, I32, P, P, I64, I32, P, I64, I32,
+                       P, I64, I64, I32, P, P],
     # fp16 arithmetic path (torch_dtype=float16 decode: run_eval.py:99, run_pseudo_labelling.py:461-463)
     "tw_gemm_f16": [P, I64, I32, P, I64, I32, P, I64, I32, I32, I32, I32, I32, I64, I64, I64, F32, P,
                     P, I64, I64, I32, I32, P, I64, I64, I32, P],

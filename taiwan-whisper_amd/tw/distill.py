@@ -120,6 +120,9 @@ class DistillationTrainer:
         if student.compute != teacher.compute:
             raise ValueError(f"student computes in {student.compute}, teacher in {teacher.compute}: the reference "
                              "runs both under one mixed_precision setting")
+        if getattr(student, "decode_weight_dtype", None) is not None:
+            raise ValueError("the student has decode_weight_dtype set: its weights change every step and the 8-bit "
+                             "copy would go stale (set it to None for training)")
         self.s, self.t = student, teacher
         self.temperature, self.kl_weight = temperature, kl_weight
         self.lr, self.b1, self.b2, self.eps = learning_rate, adam_beta1, adam_beta2, adam_epsilon

@@ -98,6 +98,11 @@ class DecodeSession:
         # separate LayerNorm
         self.gemv = B <= 8 and model.compute in ("bf16", "fp16") and d % 256 == 0
         self.gemv_ln = self.gemv and model.stream_dtype == act
+        # model.decode_weight_dtype == "fp8_e4m3": the step's Linears and the head read e4m3 bytes with one fp32 scale
+        # per weight row (tw_gemv_w8_*; the model's buffers, allocated once, so a captured step survives a
+        # requantisation); off the GEMV path the session reads a 16-bit copy of the dequantised weights, so a
+        # recording's values do not depend on its batch's size
+        self.w8 = getattr(model, "decode_weight_dtype", None) == "fp8_e4m3"
         # left-padded prompts (rows of one batch whose prompts differ in length: HF's decoder attention mask and
         # position ids): per row the first real cache row and the position offset, read on the device by
         # tw_decode_attn_ks / tw_embed_step_off.  Allocated once, refilled per window (set_pads), so a captured step
@@ -173,19 +178,35 @@ class DecodeSession:
         GEMV also appends columns >= kv[3] to the self-attention cache row (only on the GEMV path)."""
         m = self.m
         if self.gemv_ln:
-            F.gemv(x, w, out, ln_w=m.ln_param(ln + ".weight"), ln_b=m.ln_param(ln + ".bias"), bias=b, flags=flags,
-                   kv=kv)
+            self._gemv(x, w, out, ln_w=m.ln_param(ln + ".weight"), ln_b=m.ln_param(ln + ".bias"), bias=b, flags=flags,
+                       kv=kv)
         else:
             y = self._ln(x, ln, y)
             if self.gemv:
-                F.gemv(y, w, out, bias=b, flags=flags)
+                self._gemv(y, w, out, bias=b, flags=flags)
             else:
                 m._lin(y, w, b, out, flags=flags)
         return out
 
+    def _gemv(self, a, w, out, **kw):
+        """One GEMV launch; w is a 16-bit weight, or (bytes, row scales) with decode_weight_dtype on (_weight)."""
+        if isinstance(w, tuple):
+            F.gemv_w8(a, w[0], w[1], out, **kw)
+        else:
+            F.gemv(a, w, out, **kw)
+
+    def _weight(self, first, last=None, shape=None):
+        """The weight of one of the step's Linears as this session reads it: the model's 16-bit view (first .. last: a
+        fused span), or with decode_weight_dtype on its e4m3 bytes and row scales (GEMV path) / the 16-bit copy of
+        its dequantised values (GEMM path)."""
+        m = self.m
+        if self.w8:
+            return m.decode_weight_fp8(first) if self.gemv else m.decode_weight_dequantised(first)
+        return m._w16(first) if last is None else m.wspan(first, last, shape)
+
     def _lin(self, a, w, b, out, res=None, flags=F.GEMM_ROUND):
         if self.gemv:
-            F.gemv(a, w, out, bias=b, res=res, flags=flags)
+            self._gemv(a, w, out, bias=b, res=res, flags=flags)
         else:
             self.m._lin(a, w, b, out, res=res, flags=flags)
         return out
@@ -206,7 +227,7 @@ class DecodeSession:
         for i in range(m.config.decoder_layers):
             p = f"model.decoder.layers.{i}"
             # self attention: fused QKV -> staging; k, v appended to the cache
-            wqkv = m.wspan(p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d))
+            wqkv = self._weight(p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d))
             bqkv = m.wspan(p + ".self_attn.q_proj.bias", p + ".self_attn.v_proj.bias", (3 * d,))
             cache = self.self_kv[i]
             if self.gemv_ln:        # k, v written to the cache by the QKV GEMV itself
@@ -215,21 +236,24 @@ class DecodeSession:
                 self._ln_lin(x, p + ".self_attn_layer_norm", wqkv, bqkv, b.qkv, y)
                 F.kv_append(b.qkv[:, d:], 3 * d, cache, 2 * d, sb, b.M, 2 * d, t_dev, rows)
             self_attn(b, cache)
-            self._lin(o, m._w16(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x, res=x)
+            self._lin(o, self._weight(p + ".self_attn.out_proj.weight"), m._w16(p + ".self_attn.out_proj.bias"), x,
+                      res=x)
             # cross attention over the encoder frames
-            self._ln_lin(x, p + ".encoder_attn_layer_norm", m._w16(p + ".encoder_attn.q_proj.weight"),
+            self._ln_lin(x, p + ".encoder_attn_layer_norm", self._weight(p + ".encoder_attn.q_proj.weight"),
                          m._w16(p + ".encoder_attn.q_proj.bias"), b.q, y)
             cross_attn(b, i)
-            self._lin(o, m._w16(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"), x,
-                      res=x)
+            self._lin(o, self._weight(p + ".encoder_attn.out_proj.weight"), m._w16(p + ".encoder_attn.out_proj.bias"),
+                      x, res=x)
             # MLP
-            self._ln_lin(x, p + ".final_layer_norm", m._w16(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), b.h, y,
+            self._ln_lin(x, p + ".final_layer_norm", self._weight(p + ".fc1.weight"), m._w16(p + ".fc1.bias"), b.h, y,
                          flags=F.GEMM_ROUND | F.GEMM_GELU)
-            self._lin(b.h, m._w16(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
-        if head and self.gemv_ln:
-            self._ln_lin(x, "model.decoder.layer_norm", m._w16("model.decoder.embed_tokens.weight"), None, b.logits, y)
+            self._lin(b.h, self._weight(p + ".fc2.weight"), m._w16(p + ".fc2.bias"), x, res=x)
+        if head and (self.gemv_ln or (self.w8 and self.gemv)):    # the bytes have no GEMM: every GEMV session's head
+            self._ln_lin(x, "model.decoder.layer_norm", self._weight("model.decoder.embed_tokens.weight"), None,
+                         b.logits, y)
         elif head:
-            m.lm_head(self._ln(x, "model.decoder.layer_norm", y), out=b.logits)
+            m.lm_head(self._ln(x, "model.decoder.layer_norm", y), out=b.logits,
+                      E=self._weight("model.decoder.embed_tokens.weight") if self.w8 else None)
 
     def alloc_multi(self, Q):
         """Activation buffers of step_multi: Q rows each (one row of the batch, Q consecutive positions)."""
@@ -486,8 +510,9 @@ class _PromptedDecode:
 
     def _open(self, sess, model, enc, Tk, spare=0):
         """The session of `model` over this window's encoder rows: built on first use, re-projected in place after."""
-        # the K/V format is the session's for life
-        if sess is None or sess.xkv_dtype != getattr(model, "cross_kv_dtype", None):
+        # the K/V format and the weight format are the session's for life
+        if (sess is None or sess.xkv_dtype != getattr(model, "cross_kv_dtype", None)
+                or sess.w8 != (getattr(model, "decode_weight_dtype", None) == "fp8_e4m3")):
             return DecodeSession(model, enc, self.B, Tk, self.T_max, spare=spare)
         sess.set_encoder(enc)
         return sess
@@ -1189,9 +1214,12 @@ class _LongForm:
     decoders: dict = dataclasses.field(default_factory=dict)
 
     def decoder(self, P, ml, nb=1, spec=False):
-        # the two repeat options and the models' cross-attention K/V format are baked into a captured step
+        # the two repeat options and the models' cross-attention K/V and decode weight formats are baked into a
+        # captured step
         key = (P, ml, nb, spec, self.rq.repetition_penalty, self.rq.no_repeat_ngram_size,
                getattr(self.model, "cross_kv_dtype", None), getattr(self.rq.assistant, "cross_kv_dtype", None),
+               getattr(self.model, "decode_weight_dtype", None),
+               getattr(self.rq.assistant, "decode_weight_dtype", None),
                self.rq.return_token_logprobs)
         if key in self.decoders:
             self.decoders[key] = self.decoders.pop(key)      # most recently used last

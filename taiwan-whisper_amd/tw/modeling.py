@@ -296,12 +296,16 @@ class WhisperForConditionalGeneration:
             raise ValueError("fp16 arithmetic needs fp16 parameters or an fp32 master (fp16 autocast)")
         if compute == "fp32" and getattr(self, "_cross_kv_dtype", None) is not None:
             raise ValueError("cross_kv_dtype='fp8_e4m3' is set: the fp32 path keeps its K/V exact (set it to None first)")
+        if compute == "fp32" and getattr(self, "_decode_weight_dtype", None) is not None:
+            raise ValueError("decode_weight_dtype='fp8_e4m3' is set: the fp32 path keeps its weights exact (set it to "
+                             "None first)")
         self.compute = compute
         # fp32-master model: the 16-bit mirror is autocast's weight cast, in the autocast dtype
         half = torch.float16 if compute == "fp16" else torch.bfloat16
         if self.store.p32 is not None and compute != "fp32" and self.store.p16.dtype != half:
             self.store.p16 = torch.empty(self.store.total, dtype=half, device=self.device)
             F.cast_bf16(self.store.p32, self.store.p16)
+            self.requantize_decode_weights()         # the bytes follow the recast mirror
         return self
 
     @property
@@ -329,6 +333,88 @@ class WhisperForConditionalGeneration:
         if value is not None and self.compute == "fp32":
             raise ValueError("cross_kv_dtype='fp8_e4m3' needs a 16-bit compute path: compute='fp32' exists for exactness")
         self._cross_kv_dtype = value
+
+    DECODE_WEIGHT_DTYPES = (None, "auto", "fp8_e4m3")
+
+    @property
+    def decode_weight_dtype(self):
+        """Format of the weights the decode step's Linears read (every DecodeSession built for this model): None = the
+        16-bit weights; "fp8_e4m3" = OCP e4m3 bytes with one power-of-two fp32 scale per weight row
+        (include/tw_hip.h), read by tw_gemv_w8_* at batch <= 8 -- half the bytes per generated token there.  Covered:
+        every decoder-layer Linear of the step (fused self-attention QKV, self out-proj, cross q-proj, cross out-proj,
+        fc1, fc2) and the LM head (its own byte copy of the [Vp][d] table; the embedding lookup keeps the 16-bit one).
+        Biases, LayerNorms, embeddings, the cross k/v projection, the encoder, forward and training stay 16-bit.  The
+        bytes live in one buffer allocated once and rewritten in place (requantize_decode_weights), so captured
+        steps keep valid pointers.  A deployment setting, like cross_kv_dtype: the next generate call follows it."""
+        return getattr(self, "_decode_weight_dtype", None)
+
+    @decode_weight_dtype.setter
+    def decode_weight_dtype(self, value):
+        if value not in self.DECODE_WEIGHT_DTYPES:
+            raise ValueError(f"decode_weight_dtype must be None, 'auto' or 'fp8_e4m3', got {value!r}")
+        value = None if value == "auto" else value
+        if value is not None and self.compute == "fp32":
+            raise ValueError("decode_weight_dtype='fp8_e4m3' needs a 16-bit compute path: compute='fp32' exists for "
+                             "exactness")
+        self._decode_weight_dtype = value
+        self._w8_deq = {}
+        self.requantize_decode_weights()
+
+    def decode_weight_keys(self):
+        """(key, first segment, last segment, (N, K)) of every weight matrix decode_weight_dtype covers, in buffer
+        order; the key is the first segment's name."""
+        cfg, d = self.config, self.config.d_model
+        out = []
+        for i in range(cfg.decoder_layers):
+            p = f"model.decoder.layers.{i}"
+            f = cfg.decoder_ffn_dim
+            out.append((p + ".self_attn.q_proj.weight", p + ".self_attn.v_proj.weight", (3 * d, d)))
+            for n, shp in ((".self_attn.out_proj.weight", (d, d)), (".encoder_attn.q_proj.weight", (d, d)),
+                           (".encoder_attn.out_proj.weight", (d, d)), (".fc1.weight", (f, d)), (".fc2.weight", (d, f))):
+                out.append((p + n, p + n, shp))
+        out.append(("model.decoder.embed_tokens.weight", "model.decoder.embed_tokens.weight", (self.Vp, d)))
+        return [(a, a, b, shp) for a, b, shp in out]
+
+    def requantize_decode_weights(self):
+        """Rewrite the e4m3 bytes and row scales from the current 16-bit weights (tw_quant_rows_fp8), in place; a
+        no-op with decode_weight_dtype unset.  Runs when the setting is assigned, after load_state_dict /
+        from_pretrained and when set_compute recasts the mirror; call it after writing decoder weights by hand."""
+        if getattr(self, "_decode_weight_dtype", None) is None:
+            self._w8_deq = {}
+            return
+        self._w8_deq = {}                            # the dequantised 16-bit copies follow the bytes
+        if self.device.type != "cuda":
+            return                                   # a host-side model only records the setting
+        keys = self.decode_weight_keys()
+        if getattr(self, "_w8_bytes", None) is None:
+            if any(K % 16 for _, _, _, (N, K) in keys):
+                raise ValueError("decode_weight_dtype='fp8_e4m3' needs d_model and decoder_ffn_dim % 16 == 0")
+            self._w8_index, nb, ns = {}, 0, 0
+            for key, _, _, (N, K) in keys:
+                self._w8_index[key] = (nb, ns, N, K)
+                nb, ns = nb + N * K, ns + (N + 3) // 4 * 4
+            self._w8_bytes = torch.zeros(nb, dtype=torch.uint8, device=self.device)
+            self._w8_scales = torch.ones(ns, dtype=torch.float32, device=self.device)
+        for key, first, last, shp in keys:
+            b, s = self.decode_weight_fp8(key)
+            F.quant_rows_fp8(self.store.span(self.store.p16, first, last, shp), b, s)
+
+    def decode_weight_fp8(self, key):
+        """(bytes uint8 [N][K], scales fp32 [N]) views of one covered weight (decode_weight_keys)."""
+        nb, ns, N, K = self._w8_index[key]
+        return self._w8_bytes[nb: nb + N * K].view(N, K), self._w8_scales[ns: ns + N]
+
+    def decode_weight_dequantised(self, key):
+        """The 16-bit copy of one covered weight's dequantised values (bytes -> fp32 x scale -> the activation dtype,
+        exact: include/tw_hip.h), for a DecodeSession off the GEMV path: built on first use, dropped when the setting
+        is cleared or the weights are requantised."""
+        w = self._w8_deq.get(key)
+        if w is None:
+            b, s = self.decode_weight_fp8(key)
+            lut = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.device)
+            w = (lut[b.long()] * s[:, None]).to(self.act_dtype)
+            self._w8_deq[key] = w
+        return w
 
     def act_grad(self, g: torch.Tensor) -> torch.Tensor:
         """gradient entering a GEMM: rounded to the autocast dtype (the grad of a bf16 / fp16 activation),
@@ -383,6 +469,7 @@ class WhisperForConditionalGeneration:
         if strict and (missing or unexpected):
             raise RuntimeError(f"load_state_dict: missing {missing[:5]} unexpected {unexpected[:5]}")
         self._refresh_ln32()
+        self.requantize_decode_weights()
         return missing, unexpected
 
     def _refresh_ln32(self):
@@ -403,7 +490,7 @@ class WhisperForConditionalGeneration:
 
     @classmethod
     def from_pretrained(cls, path, torch_dtype=None, attn_implementation=None, low_cpu_mem_usage=True, config=None,
-                        device="cuda", compute="bf16", cross_kv_dtype=None, **kw):
+                        device="cuda", compute="bf16", cross_kv_dtype=None, decode_weight_dtype=None, **kw):
         from safetensors.torch import load_file
         cfg = config if config is not None else WhisperConfig.from_pretrained(path)
         if isinstance(cfg, dict):
@@ -412,7 +499,8 @@ class WhisperForConditionalGeneration:
         dt = torch_dtype or torch.float32
         m = cls.from_state_dict(cfg, sd, dtype=dt, device=device, compute="fp16" if dt == torch.float16 else compute)
         m.cross_kv_dtype = cross_kv_dtype
-        gp = os.path.join(path, "generation_config.json")
+        m.decode_weight_dtype = decode_weight_dtype
+        gp =os.path.join(path, "generation_config.json")
         if os.path.exists(gp):
             with open(gp) as f:
                 m.generation_config = GenerationConfig(json.load(f))
@@ -755,12 +843,14 @@ class WhisperForConditionalGeneration:
             tape.append(("ln_final", "model.decoder.layer_norm", dict(sv=sv)))
         return h
 
-    def lm_head(self, h16: torch.Tensor, out=None) -> torch.Tensor:
-        """tied proj_out: [M, d] -> logits [M, Vp] in the compute dtype (pad columns are 0)."""
+    def lm_head(self, h16: torch.Tensor, out=None, E=None) -> torch.Tensor:
+        """tied proj_out: [M, d] -> logits [M, Vp] in the compute dtype (pad columns are 0).  E: another [Vp][d] table
+        than the model's own (a DecodeSession's dequantised copy)."""
         M = h16.shape[0]
         if out is None:
             out = self._rows(M, self.Vp, self.act_dtype)
-        E = self._w16("model.decoder.embed_tokens.weight")
+        if E is None:
+            E = self._w16("model.decoder.embed_tokens.weight")
         F.gemm(h16, E, out, M, self.Vp, self.config.d_model, lda=h16.stride(0), ldb=self.config.d_model,
                ldc=self.Vp, flags=F.GEMM_ROUND, algo_N=self.config.vocab_size)
         return out
@@ -1111,4 +1201,5 @@ def random_init_(model: WhisperForConditionalGeneration, seed: int = 0, std: flo
     if st.p32 is not None:
         F.cast_bf16(st.p32, st.p16)
     model._refresh_ln32()
+    model.requantize_decode_weights()
     return model

@@ -173,6 +173,58 @@ def gemv(x, W, C, *, ln_w=None, ln_b=None, eps=1e-5, bias=None, res=None, aux=No
     return C
 
 
+def quant_rows_fp8(src, dst, scales):
+    """16-bit rows src [N][K] (row stride src.stride(0)) -> e4m3 bytes dst [N][K] (uint8, row stride dst.stride(0))
+    and one fp32 power-of-two scale per row (tw_quant_rows_fp8; the format: include/tw_hip.h)."""
+    N, K = src.shape
+    assert src.dtype in HALF and dst.dtype == torch.uint8 and scales.dtype == torch.float32
+    assert tuple(dst.shape) == (N, K) and src.stride(1) == 1 and dst.stride(1) == 1
+    if N == 0:
+        return dst, scales
+    _need(src, (N - 1) * src.stride(0) + K, "quant_rows_fp8 src")
+    _need(dst, (N - 1) * dst.stride(0) + K, "quant_rows_fp8 dst")
+    _need(scales, N, "quant_rows_fp8 scales")
+    call("tw_quant_rows_fp8", src.data_ptr(), src.stride(0), _dt(src), N, K, dst.data_ptr(), dst.stride(0),
+         scales.data_ptr(), _stream())
+    return dst, scales
+
+
+def gemv_w8(x, W8, w_scale, C, *, ln_w=None, ln_b=None, eps=1e-5, bias=None, res=None, aux=None, flags=0, kv=None):
+    """tw_gemv_w8_bf16 / tw_gemv_w8_f16: gemv() over a weight kept as e4m3 bytes W8 [N][K] (uint8) with one fp32 scale
+    per row (quant_rows_fp8); x, bias, aux and a 16-bit C are bf16 or fp16, as gemv's."""
+    M, K = x.shape
+    N = W8.shape[0]
+    h = x.dtype
+    assert h in HALF and W8.dtype == torch.uint8 and M <= 8 and W8.shape[1] == K
+    assert x.stride(1) == 1 and W8.stride(1) == 1 and w_scale.dtype == torch.float32
+    _need(W8, (N - 1) * W8.stride(0) + K, "gemv_w8 W")
+    _need(w_scale, N, "gemv_w8 scales")
+    _need(C, (M - 1) * C.stride(0) + N, "gemv_w8 C")
+    if ln_w is not None:
+        assert ln_w.dtype == torch.float32 and ln_b.dtype == torch.float32 and ln_w.numel() == K == ln_b.numel()
+    if bias is not None:
+        assert bias.dtype == h and bias.numel() >= N
+        flags |= GEMM_BIAS
+    if res is not None:
+        _need(res, (M - 1) * res.stride(0) + N, "gemv_w8 residual")
+        flags |= GEMM_RES
+    if aux is not None:
+        assert aux.dtype == h
+        _need(aux, (M - 1) * aux.stride(0) + N, "gemv_w8 aux")
+    kc, ksb, kld, kcol, kt = None, 0, 0, 0, None
+    if kv is not None:
+        kc, ksb, kld, kcol, kt, tmax = kv
+        assert kc.dtype == C.dtype and kt.dtype == torch.int32 and 0 <= kcol < N
+        _need(kc, (M - 1) * ksb + (tmax - 1) * kld + (N - kcol), "gemv_w8 kv cache")
+    KernelTimer.wrap("gemv_w8", 2.0 * M * N * K, lambda: call(
+        "tw_gemv_w8_f16" if h == torch.float16 else "tw_gemv_w8_bf16", x.data_ptr(), x.stride(0), _ptr(ln_w),
+        _ptr(ln_b), float(eps), W8.data_ptr(), W8.stride(0), w_scale.data_ptr(), C.data_ptr(), C.stride(0), _dt(C), M,
+        N, K, _ptr(bias), _ptr(res), res.stride(0) if res is not None else 0,
+        _dt(res) if res is not None else F32, _ptr(aux), aux.stride(0) if aux is not None else 0, flags,
+        _ptr(kc), ksb, kld, kcol, _ptr(kt), _stream()))
+    return C
+
+
 def layernorm_fwd(x, w, b, y, mean=None, rstd=None, eps=1e-5):
     D = x.shape[-1]
     rows = x.numel() // D

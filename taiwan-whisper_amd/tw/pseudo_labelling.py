@@ -71,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--cross_kv_dtype", type=str, default="auto", choices=["auto", "fp8_e4m3"],
                     help="cross-attention K/V cache: auto -> the compute type's 16 bits; fp8_e4m3 -> 8-bit blocks with "
                          "power-of-two scales (half the memory and bytes per token; not with float32)")
+    ap.add_argument("--decode_weight_dtype", type=str, default="auto", choices=["auto", "fp8_e4m3"],
+                    help="decoder weights read by the small-batch decode step: auto -> the compute type's 16 bits; "
+                         "fp8_e4m3 -> 8-bit rows with power-of-two scales (half the weight bytes per token at batch "
+                         "<= 8; not with float32)")
     ap.add_argument("--write_scores", type=_bool, default=False,
                     help="add the columns avg_logprob, min_logprob, compression_ratio after text (avg_logprob: "
                          "faster-whisper's, the mean log-prob of the chunk's generated tokens, eos included)")
@@ -319,7 +323,9 @@ def main(argv=None):
     model = WhisperForConditionalGeneration.from_pretrained(
         args.model_size_or_path, torch_dtype=dtype, device=torch.device("cuda", local), compute=compute)
     model.cross_kv_dtype = args.cross_kv_dtype
-    print(f"Using device: cuda:{local} ({compute}, cross K/V {args.cross_kv_dtype})", flush=True)
+    model.decode_weight_dtype = args.decode_weight_dtype
+    print(f"Using device: cuda:{local} ({compute}, cross K/V {args.cross_kv_dtype}, decode weights "
+          f"{args.decode_weight_dtype})", flush=True)
     decode = load_text_decoder(args)
     tr = ChunkTranscriber(model, args.language, args.max_new_tokens, repetition_penalty=args.repetition_penalty,
                           no_repeat_ngram_size=args.no_repeat_ngram_size)
